@@ -1,9 +1,15 @@
 """Benchmark: scans/s of the fused RANSAC + landmark + UKF hot path (BASELINE.json).
 
-python bench.py [--gpus N] [--steps K] [--warmup W]
+python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   N > 1: launched by the driver as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the result line (``value``,
+``ms_per_step``).  --dump-outputs DIR then also writes what the last timed step computed as
+DIR/<name>.npy (dump_outputs below).  --full adds every other measurement to the line: the
+CPU baseline, the instrumented pass and the ``roofline`` object, the producer alone, the
+coupled step, and at N > 1 the C4 leg.
 
 Main line (config C3 of BASELINE.json, per GPU): 4096 synthetic 720-point scans
 (SURVEY §8d generator), chunked 7x100 + 20 as functions.py:64-76 does; per
@@ -16,7 +22,7 @@ each rank owns its own 4096 scans (ids rank*4096 ...), no data-path
 collective; a host TCP group (lidar_slam_amd/hostgroup.py; no torch in the
 process) gives the barrier and the max-over-ranks of the elapsed time.
 
-C4 leg (configs[3]; at N > 1 by default, or --c4): one host batch of 65,536
+C4 leg (configs[3]; with --full at N > 1, or --c4): one host batch of 65,536
 scans in shared memory split across the ranks, H2D + pipeline + RCCL gather of
 the results to rank 0 + D2H, timed end to end (the "c4" object of the line;
 c4_leg below).
@@ -154,6 +160,47 @@ def capacity_overflows(models):
     The reference's list is unbounded (ransac_functions.py:75-76): a timed step is
     reference-exact only if this is 0."""
     return int(np.sum((models["flags"] & 256) != 0))
+
+
+DUMP_BUDGET_BYTES = 64 * 1000 * 1000  # --dump-outputs: all files together stay below this
+
+
+def output_arrays(r):
+    """What a caller of the timed path receives (ScanPipeline.results()), as plain float arrays:
+    the inlier mask (float32), the projected y, the chunk records and the landmark lists as one
+    float64 column per field (the padding fields left out; list slots at or past a scan's
+    lmk_count zeroed, as they hold no landmark), the list lengths and the UKF state.  The
+    optional diagnostic outputs (draws, trial counts, the producer's final MT19937 state) are
+    not among them: the timed pipeline is built without want_draws / want_counts / want_state,
+    so it does not compute them and results() does not return them."""
+    out = {"mask": r["mask"].astype(np.float32)}
+    if "y_proj" in r:
+        out["y_proj"] = r["y_proj"].astype(np.float64)
+    m = r["models"]
+    out["models"] = np.stack([m[n].astype(np.float64) for n in m.dtype.names if n != "reserved"], -1)
+    if "landmarks" in r:
+        lm, cnt = r["landmarks"], r["lmk_count"]
+        live = np.arange(lm.shape[1])[None, :] < cnt[:, None]
+        out["landmarks"] = np.stack([np.where(live, lm[n], 0).astype(np.float64) for n in lm.dtype.names], -1)
+        out["lmk_count"] = cnt.astype(np.float64)
+    if "ukf_x" in r:
+        out["ukf_x"] = r["ukf_x"].astype(np.float64)
+        out["ukf_P"] = r["ukf_P"].astype(np.float64)
+    return out
+
+
+def dump_outputs(path, r):
+    """Write output_arrays(r) as ``path``/<name>.npy.  If they exceed DUMP_BUDGET_BYTES together,
+    every array keeps the same fraction of its rows (first axis), picked by a fixed seed per
+    array and kept in order, so two runs with the same arguments write the same rows."""
+    arrays = output_arrays(r)
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(path, exist_ok=True)
+    for i, (name, a) in enumerate(arrays.items()):
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, int(len(a) * (DUMP_BUDGET_BYTES / total)))
+            a = a[np.sort(np.random.default_rng(20240 + i).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(n_scans, n_beams, L, procs):
@@ -484,100 +531,13 @@ def rank_device(local_rank):
     return int(v) if v not in (None, "") else int(local_rank)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--gpus", type=int, default=1)
-    # 50 steps of ~1 ms: the two-stream pipeline's fill and drain (the first producer has no
-    # consumers beside it, the last consumers no producer) amortised to ~1 % of the step
-    ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--scans", type=int, default=4096, help="scans per GPU")
-    ap.add_argument("--beams", type=int, default=720)
-    ap.add_argument("--landmarks", type=int, default=20)
-    ap.add_argument("--trials", type=int, default=100)
-    ap.add_argument("--hyp", default="mt19937", choices=["mt19937", "philox"])
-    ap.add_argument("--no-ukf", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-sample", type=int, default=2048, help="CPU baseline: at least this many scans")
-    ap.add_argument("--cpu-per-proc", type=int, default=16, help="CPU baseline: at least this many scans per process")
-    ap.add_argument("--cpu-sample-1core", type=int, default=96)
-    ap.add_argument("--cpu-procs", type=int, default=0, help="CPU baseline processes (default: every usable core)")
-    ap.add_argument("--lmk-capacity", type=int, default=64,
-                    help="per-scan landmark list capacity (>= the steady-state list, ~42 on C3)")
-    ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic_latest.json"))
-    ap.add_argument("--also-philox", action="store_true", help="also time the Philox (throughput) mode")
-    ap.add_argument("--c4", action="store_true", help="run the C4 leg (also at one GPU; default: only N > 1)")
-    ap.add_argument("--no-c4", action="store_true", help="skip the C4 leg at N > 1")
-    ap.add_argument("--c4-scans", type=int, default=65536, help="C4: scans of the one shared batch")
-    ap.add_argument("--c4-steps", type=int, default=5)
-    ap.add_argument("--c4-transport", default="rccl", choices=["rccl", "host"],
-                    help="C4 gather: RCCL (the product), or host TCP for a rehearsal whose ranks share one device")
-    ap.add_argument("--c4-timeout", type=float, default=240.0, help="seconds before the C4 leg is abandoned")
-    ap.add_argument("--no-alone", action="store_true", help="skip the producer-alone timing (profiled runs)")
-    ap.add_argument("--no-coupled", action="store_true",
-                    help="skip the coupled RANSAC->UKF step (LMK_FROM_RANSAC) of SURVEY 8(d)")
-    args = ap.parse_args()
-
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    rank = int(os.environ.get("RANK", "0"))
-    local = int(os.environ.get("LOCAL_RANK", "0"))
-    L = args.landmarks
-
-    # CPU baseline first: before anything touches the GPU (the pool forks)
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        usable, quota = usable_cpus()
-        procs = args.cpu_procs or usable
-        sample = max(args.cpu_sample, args.cpu_per_proc * procs)
-        rate1, dt1 = cpu_baseline_1core(args.cpu_sample_1core, args.beams, L)
-        rate, dt = cpu_baseline(sample, args.beams, L, procs)
-        cpu = {"value": round(rate, 2), "unit": "scans/s", "cores": procs, "kind": "port",
-               "value_1core": round(rate1, 2), "host_cpus": os.cpu_count(), "usable_cpus": usable,
-               "cgroup_cpu_quota": quota, "cpu_model": cpu_model(),
-               "sample": "%d synthetic %d-pt scans (same generator, per-scan seeds) through the NumPy twin of "
-                         "the reference (skimage-structured ransac + landmark association, oracle/numpy_twin.py) "
-                         "+ the NumPy UKF restatement (oracle/ukf.py), %d processes (one per usable core), %.2f s "
-                         "wall; 1 core: %d scans in %.1f s; twin/reference calibration in BASELINE.md"
-                         % (sample, args.beams, procs, dt, args.cpu_sample_1core, dt1)}
-
-    dist = None
-    if world > 1:
-        # the ranks' barrier / max-reduce over TCP (lidar_slam_amd.hostgroup): no torch in this
-        # process, whose bundled HIP runtime would sit beside /opt/rocm's and break RCCL
-        from lidar_slam_amd.hostgroup import HostGroup
-        dist = HostGroup(rank, world)
-
+def full_legs(args, ctx, dist, b, ukf, ids, r, elapsed, step, sync_all, barrier):
+    """--full, after the timed region (whose producer events are still in ``ctx``): the instrumented
+    pass, the coupled step, the producer alone, and the ``roofline`` object built from them.
+    ``r``: the last timed step's results; ``elapsed``: the timed region, max over ranks.
+    Returns (roofline, coupled)."""
     from lidar_slam_amd import _lib
-    from lidar_slam_amd.device import Context
-    from lidar_slam_amd.pipeline import ScanPipeline
-
-    ctx = Context(rank_device(local))
-    S = args.scans
-    ids = shard_scan_ids(rank, S)
-    b, ukf = make_workload(ids, args.beams, L, seed_base=rank)
-    pipe = ScanPipeline(ctx, b["xy"], b["scan_chunk_off"], b["chunk_pt_off"], seeds=np.array(ids, np.uint32),
-                        max_trials=args.trials, hyp=args.hyp, lmk_capacity=args.lmk_capacity, want_yproj=True,
-                        ukf=None if args.no_ukf else ukf)
-    def sync_all():
-        ctx.sync()
-
-    def barrier():
-        if dist is not None:
-            dist.barrier()
-
-    def step():
-        pipe.run(sync=False)
-
-    # warmup outside the HIP-event window, then the timed region with the dominant kernel's
-    # events on (they sit on the producer's stream).  Every event recorded on the ctx stream is
-    # a marker packet that drains it (~7 us between two kernels on the MI355X), so
-    # the consensus / whole-call events run in a separate instrumented pass after the timed one.
-    for _ in range(args.warmup):
-        step()
-    sync_all()
-    ctx.set_timing(True, kernels=[_lib.K_RNG])
-    ctx.timing_reset()
-    elapsed = timed_region(step, args.steps, 0, sync_all, barrier)
+    S, L = len(ids), args.landmarks
     rms, rl = ctx.timing(_lib.K_RNG)
     ctx.set_timing(True)
     ctx.timing_reset()
@@ -587,7 +547,6 @@ def main():
     kms, klaunch = ctx.timing(_lib.K_PIPELINE)
     cms, cl = ctx.timing(_lib.K_CONSENSUS)
     ctx.set_timing(False)
-    elapsed = reduce_max(elapsed, dist)
     kavg = reduce_max(kms / max(klaunch, 1), dist)
     ravg = reduce_max(rms / rl, dist) if rl else None
     cavg = reduce_max(cms / max(cl, 1), dist)
@@ -612,13 +571,6 @@ def main():
         ctx.set_timing(False)
         alone = reduce_max(ams / max(al, 1), dist)
 
-    # sanity: results are well-formed (every chunk fitted or flagged)
-    r = pipe.results()
-    valid = int(np.sum((r["models"]["flags"] & 1) != 0))
-    overflows = capacity_overflows(r["models"])  # of the last timed step (the lists chain across steps)
-
-    total_scans = S * world * args.steps
-    value = total_scans / elapsed
     sizes = np.diff(b["chunk_pt_off"])
     evals = int(np.sum(sizes) * args.trials)   # (point, hypothesis) pairs per step
     flops = FLOPS_PER_EVAL * evals
@@ -670,6 +622,124 @@ def main():
         "pipeline": {"ms": round(kavg, 4), "alg_bytes_per_launch": alg_bytes, "hbm_alg_gbs": round(hbm_gbs, 2),
                      "hbm_frac": round(hbm_gbs / HBM_PEAK_GBS, 5)},
     })
+    return roof, coupled
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gpus", type=int, default=1)
+    # 50 steps of ~1 ms: the two-stream pipeline's fill and drain (the first producer has no
+    # consumers beside it, the last consumers no producer) amortised to ~1 % of the step
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: CPU baseline, instrumented pass + roofline, "
+                         "producer alone, coupled step, the C4 leg at N > 1 (the --no-* options below trim it)")
+    ap.add_argument("--scans", type=int, default=4096, help="scans per GPU")
+    ap.add_argument("--beams", type=int, default=720)
+    ap.add_argument("--landmarks", type=int, default=20)
+    ap.add_argument("--trials", type=int, default=100)
+    ap.add_argument("--hyp", default="mt19937", choices=["mt19937", "philox"])
+    ap.add_argument("--no-ukf", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--cpu-sample", type=int, default=2048, help="CPU baseline: at least this many scans")
+    ap.add_argument("--cpu-per-proc", type=int, default=16, help="CPU baseline: at least this many scans per process")
+    ap.add_argument("--cpu-sample-1core", type=int, default=96)
+    ap.add_argument("--cpu-procs", type=int, default=0, help="CPU baseline processes (default: every usable core)")
+    ap.add_argument("--lmk-capacity", type=int, default=64,
+                    help="per-scan landmark list capacity (>= the steady-state list, ~42 on C3)")
+    ap.add_argument("--traffic", default=os.path.join(ROOT, "profiles", "traffic_latest.json"))
+    ap.add_argument("--also-philox", action="store_true", help="also time the Philox (throughput) mode")
+    ap.add_argument("--c4", action="store_true", help="run the C4 leg (also at one GPU; default: only --full at N > 1)")
+    ap.add_argument("--no-c4", action="store_true", help="skip the C4 leg of --full at N > 1")
+    ap.add_argument("--c4-scans", type=int, default=65536, help="C4: scans of the one shared batch")
+    ap.add_argument("--c4-steps", type=int, default=5)
+    ap.add_argument("--c4-transport", default="rccl", choices=["rccl", "host"],
+                    help="C4 gather: RCCL (the product), or host TCP for a rehearsal whose ranks share one device")
+    ap.add_argument("--c4-timeout", type=float, default=240.0, help="seconds before the C4 leg is abandoned")
+    ap.add_argument("--no-alone", action="store_true", help="skip the producer-alone timing (profiled runs)")
+    ap.add_argument("--no-coupled", action="store_true",
+                    help="skip the coupled RANSAC->UKF step (LMK_FROM_RANSAC) of SURVEY 8(d)")
+    args = ap.parse_args()
+
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    rank = int(os.environ.get("RANK", "0"))
+    local = int(os.environ.get("LOCAL_RANK", "0"))
+    L = args.landmarks
+
+    # CPU baseline first: before anything touches the GPU (the pool forks)
+    cpu = None
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
+        usable, quota = usable_cpus()
+        procs = args.cpu_procs or usable
+        sample = max(args.cpu_sample, args.cpu_per_proc * procs)
+        rate1, dt1 = cpu_baseline_1core(args.cpu_sample_1core, args.beams, L)
+        rate, dt = cpu_baseline(sample, args.beams, L, procs)
+        cpu = {"value": round(rate, 2), "unit": "scans/s", "cores": procs, "kind": "port",
+               "value_1core": round(rate1, 2), "host_cpus": os.cpu_count(), "usable_cpus": usable,
+               "cgroup_cpu_quota": quota, "cpu_model": cpu_model(),
+               "sample": "%d synthetic %d-pt scans (same generator, per-scan seeds) through the NumPy twin of "
+                         "the reference (skimage-structured ransac + landmark association, oracle/numpy_twin.py) "
+                         "+ the NumPy UKF restatement (oracle/ukf.py), %d processes (one per usable core), %.2f s "
+                         "wall; 1 core: %d scans in %.1f s; twin/reference calibration in BASELINE.md"
+                         % (sample, args.beams, procs, dt, args.cpu_sample_1core, dt1)}
+
+    dist = None
+    if world > 1:
+        # the ranks' barrier / max-reduce over TCP (lidar_slam_amd.hostgroup): no torch in this
+        # process, whose bundled HIP runtime would sit beside /opt/rocm's and break RCCL
+        from lidar_slam_amd.hostgroup import HostGroup
+        dist = HostGroup(rank, world)
+
+    from lidar_slam_amd import _lib
+    from lidar_slam_amd.device import Context
+    from lidar_slam_amd.pipeline import ScanPipeline
+
+    ctx = Context(rank_device(local))
+    S = args.scans
+    ids = shard_scan_ids(rank, S)
+    b, ukf = make_workload(ids, args.beams, L, seed_base=rank)
+    pipe = ScanPipeline(ctx, b["xy"], b["scan_chunk_off"], b["chunk_pt_off"], seeds=np.array(ids, np.uint32),
+                        max_trials=args.trials, hyp=args.hyp, lmk_capacity=args.lmk_capacity, want_yproj=True,
+                        ukf=None if args.no_ukf else ukf)
+    def sync_all():
+        ctx.sync()
+
+    def barrier():
+        if dist is not None:
+            dist.barrier()
+
+    def step():
+        pipe.run(sync=False)
+
+    # warmup, then the timed region.  With --full the dominant kernel's events are on in it (they
+    # sit on the producer's stream).  Every event recorded on the ctx stream is a marker packet
+    # that drains it (~7 us between two kernels on the MI355X), so the consensus /
+    # whole-call events run in a separate instrumented pass after the timed one (full_legs).
+    for _ in range(args.warmup):
+        step()
+    sync_all()
+    if args.full:
+        ctx.set_timing(True, kernels=[_lib.K_RNG])
+        ctx.timing_reset()
+    elapsed = reduce_max(timed_region(step, args.steps, 0, sync_all, barrier), dist)
+
+    # what the last timed step computed, before anything runs the pipeline again (the landmark
+    # lists and the UKF state chain across steps); sanity: every chunk fitted or flagged
+    r = pipe.results()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, r)
+    valid = int(np.sum((r["models"]["flags"] & 1) != 0))
+    overflows = capacity_overflows(r["models"])
+
+    roof = coupled = None
+    if args.full:
+        roof, coupled = full_legs(args, ctx, dist, b, ukf, ids, r, elapsed, step, sync_all, barrier)
+
+    total_scans = S * world * args.steps
+    value = total_scans / elapsed
 
     out = {
         "metric": "scans/sec (RANSAC+UKF, 720-pt scans) at 1/2/4/8 MI355X + HBM GB/s vs peak",
@@ -678,6 +748,8 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        # with --full the timed steps carry the producer-stream event markers, so
+        # this figure and ``value`` are then measured with them; a plain run records none
         "ms_per_step": round(elapsed / args.steps * 1e3, 4),
         "higher_is_better": True,
         "scaling": "weak",
@@ -709,7 +781,7 @@ def main():
             pipe2.run(sync=False)
         ctx.sync()
         out["philox_scans_per_s"] = round(S * args.steps / (time.perf_counter() - t0), 1)
-    if args.c4 or (world > 1 and not args.no_c4):
+    if args.c4 or (args.full and world > 1 and not args.no_c4):
         # The main line stands on its own: a C4 leg that fails is reported in it; one that does
         # not finish in --c4-timeout seconds (a collective that never completes on some node)
         # ends every rank non-zero, with the main line printed and the leg marked as timed out.

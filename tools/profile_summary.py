@@ -1,8 +1,9 @@
 """Summarise a tools/profile_session.sh run into profiles/.
 
   python tools/profile_summary.py <tag> [bench_log]
-      reads gpurun_out/prof_<tag>/{kt,fetch,write,sq1,sq2} and the bench line of the
-      same build (default gpurun_out/bench.log); writes profiles/<tag>_*
+      reads $OUT/prof_<tag>/{kt,fetch,write,sq1,sq2} and the `bench.py --full` line of the
+      same build (default $OUT/bench.log, as tools/round_profile.sh leaves it); writes
+      profiles/<tag>_*.  OUT is $LSLAM_OUT, default bench_out, as in the tools/*.sh sessions.
 
 Kernel time comes from --kernel-trace --stats; HBM traffic from separate
 --pmc FETCH_SIZE and --pmc WRITE_SIZE passes (MI355X_MICROARCH.md §HBM:
@@ -15,7 +16,7 @@ import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-OUT = os.path.join(ROOT, "gpurun_out")
+OUT = os.path.join(ROOT, os.environ.get("LSLAM_OUT") or "bench_out")
 PROF = os.path.join(ROOT, "profiles")
 
 
@@ -71,7 +72,8 @@ def main(tag, bench_log=None):
         per[k] = {"fetch_kib": f_kib, "write_kib": w_kib, "bytes_per_launch": int(2 * f_kib * 1024 + w_kib * 1024),
                   "avg_us": [float(r["AverageNs"]) / 1e3 for r in stats if sub in r["Name"]]}
     lines = ["# rocprofv3 summary: %s" % tag, "",
-             "Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline --steps 10 --warmup 2`",
+             "Command: `rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline --no-alone "
+             "--no-coupled --steps 10 --warmup 2`",
              "(PMC: separate `--pmc FETCH_SIZE` and `--pmc WRITE_SIZE` passes, --steps 3 --warmup 1)", "",
              "| kernel | calls | avg us | min us | max us | % |", "|---|---|---|---|---|---|"]
     for r in stats:
