@@ -2,17 +2,31 @@
 // Farofeiro231/LiDAR_SLAM.  See include/lidarslam.h for the reference entry
 // points each function replaces and DESIGN.md for the layout/roofline notes.
 //
+// One translation unit.  This file holds the kernels; their device code is in
+//   lslam_wave.h (wave primitives), lslam_rng.h / lslam_rng_pipe.h (MT19937, Philox, the
+//   stream parser), lslam_ransac.h (fits, residuals), lslam_ukf.h, lslam_express.h (the
+//   express-packet kernels);
+// the host side is included at the foot:
+//   lslam_hazards.h  which waits a call's producer needs (plain C++, no HIP)
+//   lslam_ctx.h      lslam_ctx, its grow-only device buffers and timers, create / destroy,
+//                    the small ABI utilities
+//   lslam_launch.h   kernel arguments, LDS layouts, the launchers, run_split, the entry
+//                    points that launch kernels
+//
 // Execution model (lslam_scan_pipeline, parity mode):
+//   seed_kernel, cut_lane_kernel (seeding stream, fresh streams only) initial MT states;
+//                  per-chunk residual cutoffs for chunk_kernel
 //   rng_kernel     (producer stream) one parser wave per scan, 4 parsers per
 //                  workgroup, each twisting its own MT blocks: the scan's chained legacy
 //                  MT19937 stream (ransac_functions.py:73 + fit.py:791) -> the
 //                  j of every Fisher-Yates step, assuming no early stop
 //                  (lslam_rng_pipe.h)
-//   resolve_reg8_kernel one wave per (chunk, 64 draws) (resolve_kernel / _walk /
-//                  _big for other sizes and epochs): steps -> the T+1 draws
+//   resolve_reg8_kernel one wave per (chunk, 64 draws): steps -> the T+1 draws
+//                  (other sizes: resolve_reg_kernel; alone on the stream: resolve_kernel, steps
+//                  staged in LDS; steps past 16 KiB and epochs: resolve_walk_kernel)
 //   chunk_kernel   one wave per chunk: A4/A5 counts (lane = hypothesis), A6 tie
 //                  sums + selection, mask + A7 refit, A8 line parameters
-//                  (chunks of > 128 points: model / count / select kernels)
+//                  (chunks of > 128 points: model_kernel, count_kernel, select_kernel)
 //   scan_kernel    (fix-up) one wave per scan; exits at once unless one of its
 //                  chunks stopped early, then replays the scan sequentially
 //   ukf_group_kernel U1-U8 on lane groups (16 lanes per scan at L = 20), 4-wave
@@ -1857,7 +1871,7 @@ static void launch_ukf_group(const KArgs &k, int n_landmarks, hipStream_t stream
 // lane each before their first twist (scalar chain + one LDS write per word: ~4.1k counted
 // instructions per scan of the producer's ~122k, SQ counters r05f).  Here 64 scans share a wave
 // (3 VALU per word for all 64).  No LDS: it runs beside the previous call's producer and
-// consumers (launch_seed), where a resident seed wave holding LDS could keep a producer
+// consumers (seed_beside), where a resident seed wave holding LDS could keep a producer
 // workgroup off its CU; each lane stores its own scan's row of out[S][624] (10 MB per C3 call,
 // merged in L2), and the producer's parsers read their rows coalesced.  Wave priority 2: above
 // the consumers, below the parsers, so it is done long before the next producer launches.
@@ -1875,7 +1889,7 @@ __global__ __launch_bounds__(64) void seed_kernel(const uint32_t *__restrict__ s
 }
 
 // The chunks' box terms and cutoffs (chunk_cut) one lane per chunk, launched with seed_kernel on
-// the seeding stream beside the previous call (launch_seed), so the consensus on the context
+// the seeding stream beside the previous call (launch_cuts), so the consensus on the context
 // stream -- the longer of the pipeline's two loops at r06 -- reads 32 bytes per
 // chunk instead of reducing its box over the wave (~220 of its ~3.3k instructions per chunk).
 // The same key maxima as cut_finish's DPP reduction, so the same ChunkCut.
@@ -3026,1710 +3040,9 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
     }
 }
 
+
 // ------------------------------------------------------------------------
-// host side
+// host side: the context, then the launchers and entry points
 // ------------------------------------------------------------------------
-constexpr int LSLAM_EV_RING = 64;
-constexpr int LSLAM_MAX_OUTS = 48;
-
-constexpr int NSLOTS = 2;  // producer slots in the ring
-struct lslam_ctx {
-    int device;
-    hipStream_t stream;
-    bool timing;
-    // per kernel id: a ring of (start, stop) event pairs harvested lazily, so
-    // timing never blocks the host between back-to-back launches
-    hipEvent_t ev0[LSLAM_K_COUNT][LSLAM_EV_RING], ev1[LSLAM_K_COUNT][LSLAM_EV_RING];
-    int head[LSLAM_K_COUNT], npend[LSLAM_K_COUNT];
-    double total_ms[LSLAM_K_COUNT];
-    int64_t launches[LSLAM_K_COUNT];
-    // main-stream scratch: resolved draws (when the caller gives no draws_out)
-    void *scr;
-    size_t scr_bytes;
-    // express-scan revolution builder scratch (per-packet flags/ranks, per-revolution info)
-    void *escr;
-    size_t escr_bytes;
-    // large-chunk consensus scratch: per-trial counts (+ Philox draws)
-    void *cscr;
-    size_t cscr_bytes;
-    // grid cap of the one-wave consumer kernels (resolve, chunk, fix-up, post)
-    int resolve_beside;  // this call's resolves will likely run beside the next call's producer
-    int n_cus;         // compute units of the device
-    uint32_t timing_mask;  // kernel ids timed when timing is on (lslam_set_timing_mask)
-    // reject tables of the table-mode parser, K = 2..127 (lslam_rng_pipe.h)
-    uint32_t *rt_all;
-    // seed_kernel -> rng_kernel: initial MT states [n_scans][624].  [0], [1]: the pipeline's, by
-    // call parity, seeded on sstream ahead of their producers (launch_seed); [2]: producers on the
-    // ctx stream (lslam_hyp_mt19937), seeded in stream order
-    uint32_t *seedst[3];
-    size_t seedst_bytes[3];
-    hipStream_t sstream;
-    hipEvent_t ev_seeded[2];     // on sstream, after seed_kernel into seedst[i]
-    hipEvent_t ev_seed_read[2];  // on pstream, after the producer that read seedst[i]
-    int seed_next;               // the pipeline's next seed buffer
-    // cut_lane_kernel -> chunk_kernel: [n_chunks] ChunkCut, a ring of four by seeded call: the
-    // buffer of call n is written after the producer of seeded call n - 2 (ev_seed_read), which
-    // waited for its slot, released by the fix-up of the mt call two before it -- after the
-    // consensus of seeded call n - 4, the buffer's previous reader
-    ChunkCut *cutb[4];
-    size_t cutb_bytes[4];
-    int cut_next;
-    size_t steps_budget;  // producer slot budget (prepare_steps)
-    // The MT producer of call k+1 runs on its own stream while call k's
-    // consumers finish on `stream`: two producer slots (Fisher-Yates steps +
-    // end-of-scan MT state), each released by an event once its consumers ran.
-    // (Measured and dropped at r04: a third slot, 0.79-0.86 vs 0.76 ms per C3 step; the resolve
-    // on a stream of its own after its producer, 0.871 vs 0.763 ms.)
-    hipStream_t pstream;
-    void *pslot[NSLOTS];
-    size_t pslot_bytes;
-    int next_slot;
-    hipEvent_t ev_slot_free[NSLOTS];  // on stream, after the slot's resolve + fix-up
-    hipEvent_t ev_produced;      // on pstream, after rng_kernel
-    hipEvent_t ev_copy;          // on stream, after the latest lslam_h2d / lslam_memset
-    // destinations written by copies since the producer last waited for ev_copy: the producer
-    // waits only if one of them is its input (seeds, CSR, MT state), so an xy upload per call
-    // overlaps the stream parse
-    struct { const void *p; size_t n; } copy_rng[32];
-    int n_copy_rng;
-    int copy_unknown;
-    hipEvent_t ev_call;          // on stream, at the end of the latest pipeline call
-    // A UKF step that does not read the call's RANSAC results runs on its own
-    // stream beside the RANSAC chain; the main stream joins it before ev_call.
-    hipStream_t ustream;
-    hipEvent_t ev_ukf;           // on ustream, after the side UKF
-    // Every buffer written by a call since the producer last waited for ev_call: the union
-    // over calls, not only the latest (the producer of call k may start once call k-2's
-    // fix-up has run).  A producer input that overlaps one of them makes it wait.
-    const void *out_ptr[LSLAM_MAX_OUTS];
-    size_t out_len[LSLAM_MAX_OUTS];
-    int n_out;
-    int out_unknown;             // the union overflowed: the producer waits for ev_call
-    // the latest call's mt_state_out, complete once ev_slot_free[prev_slot] (after its fix-up) fired
-    const void *prev_state_out;
-    int prev_slot;
-    int prev_fixed;
-    // speculative producer (map mode): a call whose only producer hazard is the previous call's
-    // mt_state_out parses from the previous producer's end state (its slot's state area) without
-    // waiting for that call's fix-up; the fix-up replays the scans it replayed (spec_dirty)
-    int speculate;            // env LSLAM_MT_SPECULATE=0: wait for the fix-up (test_gpu_speculate.py)
-    int spec_ok;              // the previous call was a one-epoch pipeline call with dirty flags
-    int spec_run;             // consecutive speculative calls (bounded by SPEC_RESYNC)
-    const uint32_t *prev_state_scr;
-    int prev_spec_scans;
-    uint8_t *spec_dirty[2];   // [n_scans] replayed-by-fix-up flags, by call parity
-    int spec_dirty_n;
-    int spec_cur;             // the buffer the latest fix-up wrote
-};
-
-static thread_local std::string g_err;
-
-static size_t default_steps_budget() { return (size_t)2 << 30; }  // lslam_set_steps_budget
-
-// rows v = 0..127 of every K = 2..127, built once per process (rt_word, lslam_rng_pipe.h)
-static const std::vector<uint32_t> &reject_tables() {
-    static const std::vector<uint32_t> t = [] {
-        std::vector<uint32_t> v((size_t)(RT_KMAX - 1) * RT_DWORDS);
-        for (uint32_t K = 2; K <= RT_KMAX; K++)
-            for (uint32_t r = 0; r < (uint32_t)RT_ROWS; r++)
-                for (uint32_t q = 0; q < (uint32_t)RT_ST; q++)
-                    v[(size_t)(K - 2) * RT_DWORDS + r * RT_ST + q] = rt_word(K, r, q);
-        return v;
-    }();
-    return t;
-}
-
-static int set_err(int code, const char *msg) {
-    g_err = msg;
-    return code;
-}
-
-#define HIPCHK(expr)                                                                  \
-    do {                                                                              \
-        hipError_t _e = (expr);                                                       \
-        if (_e != hipSuccess) {                                                       \
-            g_err = std::string(#expr) + ": " + hipGetErrorString(_e);                \
-            return LSLAM_ERR_HIP;                                                     \
-        }                                                                             \
-    } while (0)
-
-extern "C" {
-
-#define LSLAM_STR_(x) #x
-#define LSLAM_STR(x) LSLAM_STR_(x)
-#ifndef LSLAM_SRC_HASH
-#define LSLAM_SRC_HASH "0000000000000000"  // lidar_slam_amd/build.py passes the sources' sha256 prefix
-#endif
-const char *lslam_version(void) {
-    return "lidarslam-mi355x 0.3.0 (abi " LSLAM_STR(LSLAM_ABI_VERSION) ", src " LSLAM_SRC_HASH ", gfx950)";
-}
-
-const char *lslam_status_string(int st) {
-    switch (st) {
-        case LSLAM_OK: return "ok";
-        case LSLAM_ERR_ARG: return "invalid argument";
-        case LSLAM_ERR_HIP: return "HIP runtime error";
-        case LSLAM_ERR_NOMEM: return "out of memory";
-        case LSLAM_ERR_CAPACITY: return "capacity exceeded";
-        case LSLAM_ERR_UNSUPPORTED: return "unsupported";
-        default: return "unknown status";
-    }
-}
-
-const char *lslam_last_error(void) { return g_err.c_str(); }
-
-int lslam_device_count(int *n) {
-    if (!n) return LSLAM_ERR_ARG;
-    int c = 0;
-    hipError_t e = hipGetDeviceCount(&c);
-    if (e != hipSuccess) c = 0;
-    *n = c;
-    return LSLAM_OK;
-}
-
-int lslam_ctx_create(int device, lslam_ctx **out) {
-    if (!out) return LSLAM_ERR_ARG;
-    *out = nullptr;
-    int n = 0;
-    HIPCHK(hipGetDeviceCount(&n));
-    if (device < 0 || device >= n) return set_err(LSLAM_ERR_ARG, "device index out of range");
-    HIPCHK(hipSetDevice(device));
-    lslam_ctx *c = new (std::nothrow) lslam_ctx();
-    if (!c) return LSLAM_ERR_NOMEM;
-    c->device = device;
-    c->n_cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&c->n_cus, hipDeviceAttributeMultiprocessorCount, device));
-    if (c->n_cus < 1) c->n_cus = 1;
-    c->timing = false;
-    c->scr = nullptr;
-    c->scr_bytes = 0;
-    for (int i = 0; i < 3; i++) {
-        c->seedst[i] = nullptr;
-        c->seedst_bytes[i] = 0;
-    }
-    c->sstream = nullptr;
-    c->seed_next = 0;
-    for (int i = 0; i < 4; i++) {
-        c->cutb[i] = nullptr;
-        c->cutb_bytes[i] = 0;
-    }
-    c->cut_next = 0;
-    c->escr = nullptr;
-    c->escr_bytes = 0;
-    c->cscr = nullptr;
-    c->cscr_bytes = 0;
-    c->resolve_beside = 0;
-    c->timing_mask = 0xffffffffu;
-    c->rt_all = nullptr;
-    c->steps_budget = default_steps_budget();
-    c->pstream = nullptr;
-    c->ustream = nullptr;
-    for (int i = 0; i < NSLOTS; i++) c->pslot[i] = nullptr;
-    c->pslot_bytes = 0;
-    c->next_slot = 0;
-    c->speculate = 1;
-    if (const char *e = getenv("LSLAM_MT_SPECULATE")) c->speculate = atoi(e) != 0;
-    c->spec_ok = 0;
-    c->spec_run = 0;
-    c->prev_state_scr = nullptr;
-    c->prev_spec_scans = 0;
-    c->spec_dirty[0] = c->spec_dirty[1] = nullptr;
-    c->spec_dirty_n = 0;
-    c->spec_cur = 0;
-    c->n_out = 0;
-    for (int k = 0; k < LSLAM_K_COUNT; k++) {
-        c->total_ms[k] = 0;
-        c->launches[k] = 0;
-        c->head[k] = 0;
-        c->npend[k] = 0;
-        for (int r = 0; r < LSLAM_EV_RING; r++) c->ev0[k][r] = c->ev1[k][r] = nullptr;
-    }
-    hipError_t e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete c;
-        return set_err(LSLAM_ERR_HIP, hipGetErrorString(e));
-    }
-    for (int k = 0; k < LSLAM_K_COUNT; k++)
-        for (int r = 0; r < LSLAM_EV_RING; r++) {
-            HIPCHK(hipEventCreate(&c->ev0[k][r]));
-            HIPCHK(hipEventCreate(&c->ev1[k][r]));
-        }
-    // the producer's chains are the critical path: its stream gets the highest
-    // priority so that its workgroups are dispatched ahead of the previous call's
-    // consumers (resolve / consensus / post) that run beside it
-    {
-        int lo_pri = 0, hi_pri = 0;
-        if (hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri) != hipSuccess) hi_pri = 0;
-        HIPCHK(hipStreamCreateWithPriority(&c->pstream, hipStreamNonBlocking, hi_pri));
-    }
-    HIPCHK(hipStreamCreateWithFlags(&c->sstream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; i++) {
-        HIPCHK(hipEventCreateWithFlags(&c->ev_seeded[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_seed_read[i], hipEventDisableTiming));
-        HIPCHK(hipEventRecord(c->ev_seed_read[i], c->stream));
-    }
-    for (int i = 0; i < NSLOTS; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_slot_free[i], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_produced, hipEventDisableTiming));
-    HIPCHK(hipStreamCreateWithFlags(&c->ustream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_ukf, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->ev_call, hipEventDisableTiming));
-    for (int i = 0; i < NSLOTS; i++) HIPCHK(hipEventRecord(c->ev_slot_free[i], c->stream));
-    HIPCHK(hipEventRecord(c->ev_copy, c->stream));
-    HIPCHK(hipEventRecord(c->ev_call, c->stream));
-    {
-        const std::vector<uint32_t> &t = reject_tables();
-        HIPCHK(hipMalloc(&c->rt_all, t.size() * 4));
-        HIPCHK(hipMemcpy(c->rt_all, t.data(), t.size() * 4, hipMemcpyHostToDevice));
-    }
-    *out = c;
-    return LSLAM_OK;
-}
-
-int lslam_ctx_destroy(lslam_ctx *c) {
-    if (!c) return LSLAM_OK;
-    (void)hipSetDevice(c->device);
-    (void)hipStreamSynchronize(c->stream);
-    for (int k = 0; k < LSLAM_K_COUNT; k++)
-        for (int r = 0; r < LSLAM_EV_RING; r++) {
-            if (c->ev0[k][r]) (void)hipEventDestroy(c->ev0[k][r]);
-            if (c->ev1[k][r]) (void)hipEventDestroy(c->ev1[k][r]);
-        }
-    if (c->pstream) (void)hipStreamSynchronize(c->pstream);
-    if (c->ustream) (void)hipStreamSynchronize(c->ustream);
-    if (c->sstream) (void)hipStreamSynchronize(c->sstream);
-    if (c->scr) (void)hipFree(c->scr);
-    for (int i = 0; i < 3; i++)
-        if (c->seedst[i]) (void)hipFree(c->seedst[i]);
-    for (int i = 0; i < 4; i++)
-        if (c->cutb[i]) (void)hipFree(c->cutb[i]);
-    for (int i = 0; i < 2; i++) {
-        if (c->ev_seeded[i]) (void)hipEventDestroy(c->ev_seeded[i]);
-        if (c->ev_seed_read[i]) (void)hipEventDestroy(c->ev_seed_read[i]);
-    }
-    if (c->escr) (void)hipFree(c->escr);
-    if (c->cscr) (void)hipFree(c->cscr);
-    for (int i = 0; i < NSLOTS; i++)
-        if (c->pslot[i]) (void)hipFree(c->pslot[i]);
-    if (c->rt_all) (void)hipFree(c->rt_all);
-    for (int i = 0; i < 2; i++)
-        if (c->spec_dirty[i]) (void)hipFree(c->spec_dirty[i]);
-    hipEvent_t evs[6] = {c->ev_slot_free[0], c->ev_slot_free[1], c->ev_produced, c->ev_copy, c->ev_call, c->ev_ukf};
-    for (hipEvent_t e : evs)
-        if (e) (void)hipEventDestroy(e);
-    if (c->pstream) (void)hipStreamDestroy(c->pstream);
-    if (c->ustream) (void)hipStreamDestroy(c->ustream);
-    if (c->sstream) (void)hipStreamDestroy(c->sstream);
-    (void)hipStreamDestroy(c->stream);
-    delete c;
-    return LSLAM_OK;
-}
-
-int lslam_sync(lslam_ctx *c) {
-    if (!c) return LSLAM_ERR_ARG;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->pstream));
-    HIPCHK(hipStreamSynchronize(c->ustream));
-    HIPCHK(hipStreamSynchronize(c->sstream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    return LSLAM_OK;
-}
-
-int lslam_malloc(lslam_ctx *c, size_t bytes, void **p) {
-    if (!c || !p) return LSLAM_ERR_ARG;
-    HIPCHK(hipSetDevice(c->device));
-    *p = nullptr;
-    if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(p, bytes);
-    if (e == hipErrorOutOfMemory) return set_err(LSLAM_ERR_NOMEM, "hipMalloc: out of memory");
-    HIPCHK(e);
-    return LSLAM_OK;
-}
-
-int lslam_free(lslam_ctx *c, void *p) {
-    if (!c) return LSLAM_ERR_ARG;
-    if (!p) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipFree(p));
-    return LSLAM_OK;
-}
-
-int lslam_host_alloc(size_t bytes, void **p) {
-    if (!p) return LSLAM_ERR_ARG;
-    HIPCHK(hipHostMalloc(p, bytes ? bytes : 16, hipHostMallocDefault));
-    return LSLAM_OK;
-}
-
-int lslam_host_free(void *p) {
-    if (p) HIPCHK(hipHostFree(p));
-    return LSLAM_OK;
-}
-
-static void note_copy(lslam_ctx *c, const void *p, size_t n) {
-    if (!p || !n) return;
-    for (int i = 0; i < c->n_copy_rng; i++)
-        if (c->copy_rng[i].p == p && c->copy_rng[i].n == n) return;
-    if (c->n_copy_rng == 32) {
-        c->copy_unknown = 1;
-        return;
-    }
-    c->copy_rng[c->n_copy_rng].p = p;
-    c->copy_rng[c->n_copy_rng].n = n;
-    c->n_copy_rng++;
-}
-
-int lslam_h2d(lslam_ctx *c, void *dst, const void *src, size_t n) {
-    if (!c || (!dst && n) || (!src && n)) return LSLAM_ERR_ARG;
-    if (!n) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    // (the previous calls, which may still read dst, are ahead of this on the ctx stream)
-    HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->ev_copy, c->stream));
-    note_copy(c, dst, n);
-    return LSLAM_OK;
-}
-
-int lslam_d2h(lslam_ctx *c, void *dst, const void *src, size_t n) {
-    if (!c || (!dst && n) || (!src && n)) return LSLAM_ERR_ARG;
-    if (!n) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    // (the previous calls, which may still read dst, are ahead of this on the ctx stream)
-    HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->stream));
-    return LSLAM_OK;
-}
-
-int lslam_d2d(lslam_ctx *c, void *dst, const void *src, size_t n) {
-    if (!c || (!dst && n) || (!src && n)) return LSLAM_ERR_ARG;
-    if (!n) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    // (the previous calls, which may still read dst, are ahead of this on the ctx stream)
-    HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(hipEventRecord(c->ev_copy, c->stream));
-    note_copy(c, dst, n);
-    return LSLAM_OK;
-}
-
-int lslam_host_register(void *p, size_t n) {
-    if (!p || !n) return LSLAM_ERR_ARG;
-    const hipError_t e = hipHostRegister(p, n, hipHostRegisterDefault);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();  // not sticky: the caller falls back to pageable copies
-        return set_err(LSLAM_ERR_HIP, hipGetErrorString(e));
-    }
-    return LSLAM_OK;
-}
-
-int lslam_host_unregister(void *p) {
-    if (!p) return LSLAM_ERR_ARG;
-    HIPCHK(hipHostUnregister(p));
-    return LSLAM_OK;
-}
-
-int lslam_ctx_stream(lslam_ctx *c, void **stream) {
-    if (!c || !stream) return LSLAM_ERR_ARG;
-    *stream = (void *)c->stream;
-    return LSLAM_OK;
-}
-
-int lslam_abi_sizes(int64_t *sizes, int n) {
-    const int64_t s[7] = {(int64_t)sizeof(lslam_chunk_model), (int64_t)sizeof(lslam_landmark),
-                          (int64_t)sizeof(lslam_ransac_params), (int64_t)sizeof(lslam_ukf_params),
-                          (int64_t)sizeof(lslam_scan_batch), (int64_t)sizeof(lslam_express_measures),
-                          (int64_t)sizeof(lslam_express_revs)};
-    for (int i = 0; i < n && i < 7 && sizes; i++) sizes[i] = s[i];
-    return 7;
-}
-
-int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
-    if (!c || (!dst && n)) return LSLAM_ERR_ARG;
-    if (!n) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    // (the previous calls, which may still read dst, are ahead of this on the ctx stream)
-    HIPCHK(hipMemsetAsync(dst, v, n, c->stream));
-    HIPCHK(hipEventRecord(c->ev_copy, c->stream));
-    note_copy(c, dst, n);
-    return LSLAM_OK;
-}
-
-// fold the oldest `keep_free` pending event pairs (all of them if < 0) into the totals
-static int harvest(lslam_ctx *c, int k, int upto_free = -1) {
-    while (c->npend[k] > 0 && (upto_free < 0 || LSLAM_EV_RING - c->npend[k] < upto_free)) {
-        const int r = (c->head[k] - c->npend[k] + LSLAM_EV_RING) % LSLAM_EV_RING;
-        HIPCHK(hipEventSynchronize(c->ev1[k][r]));
-        float ms = 0.f;
-        HIPCHK(hipEventElapsedTime(&ms, c->ev0[k][r], c->ev1[k][r]));
-        c->total_ms[k] += ms;
-        c->launches[k] += 1;
-        c->npend[k] -= 1;
-    }
-    return LSLAM_OK;
-}
-
-static int timer_begin(lslam_ctx *c, int k, hipStream_t st_ = nullptr) {
-    if (!c->timing || !((c->timing_mask >> k) & 1u)) return LSLAM_OK;
-    int st = harvest(c, k, 1);
-    if (st) return st;
-    HIPCHK(hipEventRecord(c->ev0[k][c->head[k]], st_ ? st_ : c->stream));
-    return LSLAM_OK;
-}
-
-static int timer_end(lslam_ctx *c, int k, hipStream_t st_ = nullptr) {
-    if (!c->timing || !((c->timing_mask >> k) & 1u)) return LSLAM_OK;
-    HIPCHK(hipEventRecord(c->ev1[k][c->head[k]], st_ ? st_ : c->stream));
-    c->head[k] = (c->head[k] + 1) % LSLAM_EV_RING;
-    c->npend[k] += 1;
-    return LSLAM_OK;
-}
-
-int lslam_set_timing(lslam_ctx *c, int en) {
-    if (!c) return LSLAM_ERR_ARG;
-    c->timing = en != 0;
-    return LSLAM_OK;
-}
-
-int lslam_set_timing_mask(lslam_ctx *c, uint32_t mask) {
-    if (!c) return LSLAM_ERR_ARG;
-    c->timing_mask = mask;
-    return LSLAM_OK;
-}
-
-int lslam_timing(lslam_ctx *c, int k, double *ms, int64_t *n) {
-    if (!c || k < 0 || k >= LSLAM_K_COUNT) return LSLAM_ERR_ARG;
-    HIPCHK(hipSetDevice(c->device));
-    int st = harvest(c, k);
-    if (st) return st;
-    if (ms) *ms = c->total_ms[k];
-    if (n) *n = c->launches[k];
-    return LSLAM_OK;
-}
-
-int lslam_timing_reset(lslam_ctx *c) {
-    if (!c) return LSLAM_ERR_ARG;
-    for (int k = 0; k < LSLAM_K_COUNT; k++) {
-        int st = harvest(c, k);
-        if (st) return st;
-        c->total_ms[k] = 0;
-        c->launches[k] = 0;
-    }
-    return LSLAM_OK;
-}
-
-int lslam_ransac_params_default(lslam_ransac_params *p) {
-    if (!p) return LSLAM_ERR_ARG;
-    memset(p, 0, sizeof(*p));
-    p->residual_threshold = 20.0;  // ransac_functions.py:9
-    p->max_trials = 100;           // :10
-    p->min_samples = 2;            // :11
-    p->hyp_source = LSLAM_HYP_MT19937;
-    p->life = 40;                  // landmarking.py:3
-    p->tol_a = 0.1;                // :4
-    p->tol_b = 10.0;               // :5
-    p->tol_dist = 100.0;           // :6
-    p->philox_seed = 0x5eed5eedull;
-    return LSLAM_OK;
-}
-
-int lslam_ukf_params_default(lslam_ukf_params *p, int32_t L) {
-    if (!p || L < 0) return LSLAM_ERR_ARG;
-    memset(p, 0, sizeof(*p));
-    p->n_landmarks = L;
-    p->flags = LSLAM_UKF_PREDICT | LSLAM_UKF_UPDATE;
-    p->dt = 0.005;          // systemClass.py:10
-    p->wheel_radius = 50;   // UKFMethods.py:6
-    p->wheel_base = 200;    // UKFMethods.py:7
-    p->alpha = 1e-4;        // systemClass.py:20
-    p->beta = 2.0;
-    p->kappa = 0.0;
-    for (int i = 0; i < 9; i++) p->Q[i] = (i % 4 == 0) ? 0.001 : 0.0;  // systemClass.py:29
-    return LSLAM_OK;
-}
-
-double lslam_inlier_cutoff(double thr) {
-    if (isnan(thr)) return NAN;
-    if (!(thr > 0)) return 0.0;
-    if (isinf(thr)) return INFINITY;
-    double e = thr * thr;
-    while (e > 0 && sqrt(e) >= thr) e = nextafter(e, 0.0);
-    while (sqrt(e) < thr) e = nextafter(e, INFINITY);
-    return e;
-}
-
-int lslam_ukf_weights(const lslam_ukf_params *p, double *Wm, double *Wc, double *lpn) {
-    if (!p || !Wm || !Wc) return LSLAM_ERR_ARG;
-    // filterpy MerweScaledSigmaPoints._compute_weights, n = 3
-    const double n = 3.0;
-    const double lambda_ = p->alpha * p->alpha * (n + p->kappa) - n;
-    const double c = .5 / (n + lambda_);
-    for (int i = 0; i < 7; i++) Wm[i] = Wc[i] = c;
-    Wc[0] = lambda_ / (n + lambda_) + (1 - p->alpha * p->alpha + p->beta);
-    Wm[0] = lambda_ / (n + lambda_);
-    if (lpn) *lpn = lambda_ + n;
-    return LSLAM_OK;
-}
-
-int lslam_mt_seed_state(uint32_t seed, uint32_t *st) {
-    if (!st) return LSLAM_ERR_ARG;
-    for (int i = 0; i < 624; i++) {
-        st[i] = seed;
-        seed = 1812433253u * (seed ^ (seed >> 30)) + (uint32_t)(i + 1);
-    }
-    st[624] = 624;
-    return LSLAM_OK;
-}
-
-}  // extern "C"
-
-// ---- launch plumbing ----
-static inline int align16(int x) { return (x + 15) & ~15; }
-
-static int validate_batch(const lslam_scan_batch *b, bool need_points) {
-    if (!b) return set_err(LSLAM_ERR_ARG, "batch is NULL");
-    if (b->n_scans < 0 || b->n_chunks < 0 || b->n_points < 0) return set_err(LSLAM_ERR_ARG, "negative sizes");
-    if (b->n_scans == 0) return LSLAM_OK;
-    if (!b->scan_chunk_off || !b->chunk_pt_off) return set_err(LSLAM_ERR_ARG, "missing CSR offsets");
-    if (need_points && !b->xy && (!b->theta_deg || !b->dist_mm) && b->n_points > 0)
-        return set_err(LSLAM_ERR_ARG, "missing points (xy, or theta_deg + dist_mm)");
-    if (b->max_chunk_points < 0 || b->max_scan_chunks < 0) return set_err(LSLAM_ERR_ARG, "bad maxima");
-    return LSLAM_OK;
-}
-
-#if defined(LSLAM_STAMPS) || defined(LSLAM_CENSUS)
-static unsigned long long *g_wcen = nullptr;  // wave census (diagnostic builds)
-static unsigned int *g_wcen_n = nullptr;
-static unsigned int g_wcen_cap = 0;
-static unsigned int g_call_seq = 0;
-extern "C" int lslam_debug_set_census(unsigned long long *dev_buf, unsigned int *dev_count, unsigned int cap) {
-    g_wcen = dev_buf;
-    g_wcen_n = dev_count;
-    g_wcen_cap = cap;
-    return LSLAM_OK;
-}
-#endif
-#ifdef LSLAM_STAMPS
-static unsigned long long *g_dbg = nullptr;
-extern "C" int lslam_debug_set_stamps(unsigned long long *dev_buf) {
-    g_dbg = dev_buf;
-    return LSLAM_OK;
-}
-#endif
-
-static int build_args(KArgs &k, const lslam_scan_batch *b, const lslam_ransac_params *p, const lslam_ukf_params *u,
-                      int mode, int &lds) {
-    memset(&k, 0, sizeof(k));
-#ifdef LSLAM_STAMPS
-    k.dbg = g_dbg;
-#endif
-#if defined(LSLAM_STAMPS) || defined(LSLAM_CENSUS)
-    k.wcen = g_wcen;
-    k.wcen_n = g_wcen_n;
-    k.wcen_cap = g_wcen_cap;
-    k.call_seq = g_call_seq;
-#endif
-    k.b = *b;
-    if (p) {
-        if (p->min_samples != 2) return set_err(LSLAM_ERR_UNSUPPORTED, "only min_samples == 2 (ransac_functions.py:11)");
-        if (p->residual_threshold < 0) return set_err(LSLAM_ERR_ARG, "`residual_threshold` must be greater than zero");
-        if (p->max_trials < 0) return set_err(LSLAM_ERR_ARG, "`max_trials` must be greater than zero");
-        if (p->max_trials > 65533) return set_err(LSLAM_ERR_UNSUPPORTED, "max_trials > 65533");
-        if (p->hyp_source < 0 || p->hyp_source > 2) return set_err(LSLAM_ERR_ARG, "bad hyp_source");
-        if (p->hyp_source == LSLAM_HYP_EXPLICIT && !b->hyp) return set_err(LSLAM_ERR_ARG, "explicit hyp without hyp");
-        k.thr = p->residual_threshold;
-        k.ecut = lslam_inlier_cutoff(p->residual_threshold);
-        k.ecut_q = std::sqrt(k.ecut) * 1.01 + 1.0;
-        k.tol_a = p->tol_a;
-        k.tol_b = p->tol_b;
-        k.tol_dist = p->tol_dist;
-        k.tol_dist_sq = sqrt_le_bound(p->tol_dist);
-        k.philox_seed = p->philox_seed;
-        k.T = p->max_trials;
-        k.hyp_source = p->hyp_source;
-        k.life = p->life;
-    }
-    if ((mode & MODE_ASSOC) && b->landmarks && !b->lmk_count) return set_err(LSLAM_ERR_ARG, "landmarks without lmk_count");
-    const int N = b->max_chunk_points > 0 ? b->max_chunk_points : 1;
-    const int T = k.T;
-    int off = 0;
-    if (mode & (MODE_RANSAC | MODE_HYP_ONLY)) {
-        k.off_pts = off; off += align16(16 * N);
-        k.off_key = off; off += align16(4 * 624);
-        // phase-exclusive scratch shares one region: the draw-resolution tables
-        // (draw generation), then the tie sums (selection)
-        const int nxt_bytes = 4 * mt_nslot(N) * N;
-        const int uni_bytes = max(nxt_bytes, 8 * (T > 0 ? T : 1));
-        k.off_ring = off;
-        k.off_tsum = off;
-        off += align16(uni_bytes);
-        k.off_j1 = off;
-        off += align16(4 * mt_nslot(N));
-        k.off_draws = off; off += align16(8 * (T + 1));
-        k.off_cnt = off; off += align16(4 * (T > 0 ? T : 1));
-        k.off_tied = off; off += align16(4 * (T > 0 ? T : 1));
-        k.off_mask = off; off += align16(N);
-        k.off_vstack = off; off += (N > 128) ? align16(8 * 64 * 24) : 0;
-        k.off_nstack = off; off += (N > 128) ? align16(4 * 72) : 0;
-        k.off_recs = -1;
-    } else {
-        // post pass (association / UKF over fitted models): only the chunk's mask
-        k.off_mask = off; off += align16(N);
-        // and the scan's chunk records + offsets, staged up front (post_assoc_fast)
-        const int msc = b->max_scan_chunks > 0 ? b->max_scan_chunks : 1;
-        if (msc <= 256) {
-            k.off_recs = off;
-            off += align16((int)sizeof(lslam_chunk_model) * msc) + align16(4 * (msc + 1));
-        } else {
-            k.off_recs = -1;
-        }
-    }
-    // the UKF runs after the last chunk: its scratch aliases the RANSAC scratch
-    // above (offset 0); only the persistent region below (chunk history, chunk
-    // origins, landmark list) is live across both
-    if (u && u->n_landmarks > 0) {
-        k.off_ukf = 0;
-        off = max(off, align16(8 * UkfLds::doubles(u->n_landmarks)));
-    }
-    k.hist_cap = b->max_scan_chunks > 0 ? b->max_scan_chunks : 1;
-    k.off_snap = off; off += (mode & MODE_RANSAC) ? align16(4 * MT_N) : 0;
-    k.corg_cap = k.hist_cap;
-    k.off_corg = off; off += align16(16 * k.corg_cap);
-    k.off_zobs = off; off += (u && (u->flags & LSLAM_UKF_MAP)) ? align16(16 * k.corg_cap) : 0;
-    k.lmk_cap = (mode & MODE_ASSOC) ? b->lmk_capacity : 0;
-    if ((mode & MODE_ASSOC) && k.lmk_cap <= 0) return set_err(LSLAM_ERR_ARG, "lmk_capacity must be > 0");
-    // the association-only post pass keeps a list of at most 64 entries in registers
-    k.lmk_reg = (mode == MODE_ASSOC && k.lmk_cap > 0 && k.lmk_cap <= 64 && k.off_recs >= 0 &&
-                 !(u && (u->flags & LSLAM_UKF_MAP)) && b->landmarks) ? 1 : 0;
-    k.off_lmk = off; off += k.lmk_reg ? 0 : align16((int)sizeof(lslam_landmark) * (k.lmk_cap > 0 ? k.lmk_cap : 1));
-    k.off_vis = off; off += k.lmk_reg ? 0 : align16(8 * ((k.lmk_cap + 63) / 64 + 1));
-    k.pts_cap = N;
-    if (u) {
-        if (u->n_landmarks <= 0) return set_err(LSLAM_ERR_ARG, "n_landmarks must be > 0");
-        const bool map = (u->flags & LSLAM_UKF_MAP) != 0;
-        if (!b->ukf_x || !b->ukf_P || !b->ukf_u || !b->ukf_R_diag || (!map && (!b->ukf_z || !b->ukf_lmk)))
-            return set_err(LSLAM_ERR_ARG, "UKF buffers missing");
-        if (map && (!(mode & MODE_ASSOC) || !b->landmarks))
-            return set_err(LSLAM_ERR_ARG, "LSLAM_UKF_MAP needs the landmark lists (the map) in lslam_scan_pipeline");
-        if (map && u->n_landmarks < b->max_scan_chunks)
-            return set_err(LSLAM_ERR_CAPACITY, "LSLAM_UKF_MAP: n_landmarks (measurement slots) < max_scan_chunks");
-        double lpn = 0;
-        lslam_ukf_weights(u, k.ukf.Wm, k.ukf.Wc, &lpn);
-        for (int i = 0; i < 7; i++)
-            if (k.ukf.Wc[i] == 0.0) return set_err(LSLAM_ERR_UNSUPPORTED, "zero covariance weight");
-        k.ukf.cfac = lpn;
-        k.ukf.dt = u->dt;
-        k.ukf.wr = u->wheel_radius;
-        k.ukf.wb = u->wheel_base;
-        for (int i = 0; i < 9; i++) k.ukf.Q[i] = u->Q[i];
-        k.ukf.L = u->n_landmarks;
-        k.ukf.flags = u->flags;
-    }
-    lds = off;
-    if (lds > 160 * 1024) return set_err(LSLAM_ERR_CAPACITY, "chunk/trial/landmark sizes exceed the 160 KiB LDS");
-    return LSLAM_OK;
-}
-
-template <int MODE>
-static hipError_t launch_mode(const KArgs &k, int lds, hipStream_t st) {
-    const dim3 grid((unsigned)k.b.n_scans), block(64);
-    switch (k.hyp_source) {
-        case LSLAM_HYP_PHILOX:
-            hipLaunchKernelGGL((scan_kernel<LSLAM_HYP_PHILOX, MODE>), grid, block, lds, st, k);
-            break;
-        case LSLAM_HYP_EXPLICIT:
-            hipLaunchKernelGGL((scan_kernel<LSLAM_HYP_EXPLICIT, MODE>), grid, block, lds, st, k);
-            break;
-        default:
-            hipLaunchKernelGGL((scan_kernel<LSLAM_HYP_MT19937, MODE>), grid, block, lds, st, k);
-            break;
-    }
-    return hipGetLastError();
-}
-
-template <int MODE>
-static int run_scan_kernel(lslam_ctx *c, const KArgs &k, int lds, int timer) {
-    HIPCHK(hipSetDevice(c->device));
-    if (k.b.n_scans == 0) return LSLAM_OK;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        const int mx = 160 * 1024;
-        (void)hipFuncSetAttribute((const void *)scan_kernel<0, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        (void)hipFuncSetAttribute((const void *)scan_kernel<1, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        (void)hipFuncSetAttribute((const void *)scan_kernel<2, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, mx);
-        set_max_lds(scan_kernel_w4<LSLAM_HYP_EXPLICIT, MODE>);
-    });
-    int st = timer_begin(c, timer);
-    if (st) return st;
-    if (MODE == MODE_UKF && !(k.ukf.flags & LSLAM_UKF_MAP)) {  // stand-alone UKF: lane groups
-        launch_ukf_group(k, k.ukf.L, c->stream, false);
-        HIPCHK(hipGetLastError());
-    } else if (MODE == MODE_ASSOC || MODE == MODE_UKF) {  // stand-alone association / UKF: no producer beside them
-        hipLaunchKernelGGL((scan_kernel_w4<LSLAM_HYP_EXPLICIT, MODE>), dim3((unsigned)k.b.n_scans), dim3(64), lds,
-                           c->stream, k);
-        HIPCHK(hipGetLastError());
-    } else {
-        HIPCHK(launch_mode<MODE>(k, lds, c->stream));
-    }
-    st = timer_end(c, timer);
-    if (st) return st;
-    return LSLAM_OK;
-}
-
-
-// chunk_kernel LDS: one chunk's points, draws and consensus scratch
-static int layout_chunk(KArgs &k, const lslam_scan_batch *b, int &lds) {
-    const int N = b->max_chunk_points > 0 ? b->max_chunk_points : 1;
-    const int T = k.T;
-    int off = 0;
-    k.off_pts = off; off += align16(16 * N);
-    k.off_draws = off; off += (k.hyp_source == LSLAM_HYP_PHILOX) ? align16(8 * (T + 1)) : 0;  // else read in place
-    k.off_cnt = off; off += align16(4 * (T > 0 ? T : 1));
-    k.off_tied = off; off += align16(4 * (T > 0 ? T : 1));
-    k.off_tsum = off; off += align16(8 * (T > 0 ? T : 1));  // tie sums
-    k.off_mask = off; off += align16(N);
-    k.off_vstack = off; off += (N > 128) ? align16(8 * 64 * 24) : 0;
-    k.off_nstack = off; off += (N > 128) ? align16(4 * 72) : 0;
-    k.off_vtmp = off;  // (pairwise sums from registers: pw_sum_regs)
-    lds = off;
-    if (lds > 160 * 1024) return set_err(LSLAM_ERR_CAPACITY, "chunk/trial sizes exceed the 160 KiB LDS");
-    return LSLAM_OK;
-}
-
-// rng_kernel LDS: two raw MT blocks + flags
-static int layout_rng(KArgs &k, const lslam_scan_batch *b, int &lds) {
-    const int N = b->max_chunk_points > 3 ? b->max_chunk_points : 3;
-    if (N > 65536) return set_err(LSLAM_ERR_UNSUPPORTED, "chunks of more than 65536 points");
-    int off = 0;
-    k.off_blk = off; off += align16(4 * (2 * 624 + 64));  // two block slots + the head pad
-    k.rng_pipe_bytes = off;
-    lds = off * RNG_PPW;
-    // two K claims (16 B) + two reject tables shared by the workgroup's parsers, after the
-    // pipes: table mode is chosen per chunk (N - 1 <= RT_KMAX), so a batch whose largest chunk
-    // is bigger may still parse its small chunks with them
-    k.off_stbl = lds;
-    lds += 16 + 2 * 4 * RT_DWORDS;
-    return LSLAM_OK;
-}
-
-// consumer grids: one workgroup per item, at most 2^30 (kernels loop over their items)
-static inline unsigned launch_cap(const lslam_ctx *c, int64_t n) {
-    (void)c;
-    return (unsigned)(n < (1 << 30) ? (n > 0 ? n : 1) : (1 << 30));
-}
-
-static int ensure_scratch(lslam_ctx *c, size_t bytes) {
-    if (c->scr_bytes >= bytes) return LSLAM_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    HIPCHK(hipStreamSynchronize(c->pstream));
-    if (c->scr) HIPCHK(hipFree(c->scr));
-    c->scr = nullptr;
-    c->scr_bytes = 0;
-    hipError_t e = hipMalloc(&c->scr, bytes);
-    if (e == hipErrorOutOfMemory) return set_err(LSLAM_ERR_NOMEM, "hipMalloc: out of memory (step scratch)");
-    HIPCHK(e);
-    c->scr_bytes = bytes;
-    return LSLAM_OK;
-}
-
-// allow up to 160 KiB of LDS per workgroup (static + dynamic); a failure here must
-// not linger as the runtime's last error for the next launch check
-template <typename F>
-static void set_max_lds(F *fn) {
-    hipFuncAttributes at;
-    size_t stat = 0;
-    if (hipFuncGetAttributes(&at, (const void *)fn) == hipSuccess) stat = at.sharedSizeBytes;
-    (void)hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(160 * 1024 - stat));
-    (void)hipGetLastError();
-}
-
-// Producer slot: one j per Fisher-Yates step (D * n_points entries; chunk c at
-// D * chunk_pt_off[c]; + slack for 16-byte staging loads) and the end-of-scan
-// MT state.  The resolved draws live in the main-stream scratch unless the
-// caller asked for draws_out.
-// Epochs: when every scan is one chunk (C5) and the steps of all T + 1 draws
-// exceed the slot budget (lslam_set_steps_budget, default 2 GiB), the producer
-// runs in launches of ep_nd draws, each resolved before its slot is reused; the
-// MT state chains through the slots' state areas.  k.ep_count launches.
-static int prepare_steps(lslam_ctx *c, KArgs &k, int slot) {
-    const int N = k.b.max_chunk_points;
-    k.j8 = N <= 256 ? 1 : 0;
-    const size_t per_draw = (size_t)(k.b.n_points > 0 ? k.b.n_points : 1) * (k.j8 ? 1 : 2);
-    const size_t budget = c->steps_budget;
-    const int D = k.T + 1;
-    int De = D;
-    if (k.b.max_scan_chunks == 1 && (size_t)D * per_draw > budget) {
-        const size_t fit = budget / per_draw;
-        De = fit < 1 ? 1 : (fit < (size_t)D ? (int)fit : D);
-    }
-    k.ep_nd = De < D ? De : 0;
-    k.ep_d0 = 0;
-    k.ep_count = (D + De - 1) / De;
-    const size_t jbytes = ((size_t)De * per_draw + JBUF_FRONT + 64 + 255) & ~(size_t)255;
-    const size_t sbytes = ((size_t)(k.b.n_scans > 0 ? k.b.n_scans : 1) * 625 * 4 + 255) & ~(size_t)255;
-    if (c->pslot_bytes < jbytes + sbytes) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipStreamSynchronize(c->pstream));
-        for (int i = 0; i < NSLOTS; i++) {
-            if (c->pslot[i]) HIPCHK(hipFree(c->pslot[i]));
-            c->pslot[i] = nullptr;
-        }
-        c->pslot_bytes = 0;
-        for (int i = 0; i < NSLOTS; i++) {
-            hipError_t e = hipMalloc(&c->pslot[i], jbytes + sbytes);
-            if (e == hipErrorOutOfMemory) return set_err(LSLAM_ERR_NOMEM, "hipMalloc: out of memory (producer slot)");
-            HIPCHK(e);
-        }
-        c->pslot_bytes = jbytes + sbytes;
-        c->spec_ok = 0;  // the previous producer's end state went with the old slots
-    }
-    k.jbuf = (unsigned char *)c->pslot[slot] + JBUF_FRONT;
-    k.state_scr = (uint32_t *)((unsigned char *)c->pslot[slot] + jbytes);
-    k.slot_jbytes = jbytes;
-    if (k.b.draws_out) {
-        k.draws_scr = k.b.draws_out;
-    } else {
-        int st = ensure_scratch(c, (size_t)(k.b.n_chunks > 0 ? k.b.n_chunks : 1) * 2 * (k.T + 1) * 4);
-        if (st) return st;
-        k.draws_scr = (int32_t *)c->scr;
-    }
-    return LSLAM_OK;
-}
-
-// resolve_kernel LDS: the chunk's staged steps (if they fit)
-static int launch_resolve(lslam_ctx *c, const KArgs &base, hipStream_t rs) {
-    if (base.b.n_chunks == 0) return LSLAM_OK;
-    KArgs k = base;
-    const int N = k.b.max_chunk_points > 3 ? k.b.max_chunk_points : 3;
-    const int esz = k.j8 ? 1 : 2;
-    // stage a chunk's steps in LDS when they fit 16 KiB (C3: 101 x 99 B), else stream them from HBM
-    const int De = k.ep_nd > 0 ? k.ep_nd : k.T + 1;  // draws of this launch
-    const int64_t need = ((int64_t)De * (N - 1) * esz + 46) & ~(int64_t)15;  // + alignment skew
-    const int lds = need <= 16 * 1024 ? (int)need : 0;
-    k.res_g = lds;  // staging capacity in bytes
-    if (lds == 0) {  // steps streamed from HBM, waves over (chunk, draw)
-        const int64_t items = (int64_t)k.b.n_chunks * De;
-        // beside the next epoch's producer (produce_draws): four waves per SIMD beside its four
-        // parsers.  The epoch loop is max(producer, resolve beside it): with the double-buffered
-        // walk, three waves per SIMD measured 65.7-66.1 vs 68.9-69.3 ms per C5 call at two (r06d,
-        // four: 66.0-66.3); once mask-mode runs crossed block ends (r06f: a 9 % faster producer)
-        // the resolve was the longer again, and four gave 61.4-61.6 vs 63.5-63.6 ms at three.
-        // (At r02, with five producer waves per SIMD, three displaced parser workgroups: 107 vs
-        // 78 ms.  Measured and dropped: LDS tiles of [64 draws][128 steps], 1.0 vs 0.43 ms per
-        // epoch.)
-        const int64_t cap = k.ep_count > 1 ? 16 * (int64_t)c->n_cus : (1 << 20);
-        const dim3 grid(launch_cap(c, items > cap ? cap : items)), block(64);
-        if (k.j8) hipLaunchKernelGGL((resolve_walk_kernel<uint8_t, 16>), grid, block, 0, rs, k);
-        else hipLaunchKernelGGL((resolve_walk_kernel<uint16_t, 16>), grid, block, 0, rs, k);
-        HIPCHK(hipGetLastError());
-        return LSLAM_OK;
-    }
-    if (k.j8 && c->resolve_beside) {  // no LDS: the producer's workgroups hold most of it
-        if (N - 1 <= 16 * RR_GROUPS - 1) {
-            // draws of this launch to resolve per chunk: all but draw T (never read by the
-            // consensus) unless the caller wants the draws
-            const bool has_last = k.ep_d0 + De == k.T + 1;
-            const int Dres = (has_last && !k.b.draws_out && De > 1) ? De - 1 : De;
-            if ((int64_t)k.b.n_chunks * Dres >= ((int64_t)1 << 31) - 64)
-                return set_err(LSLAM_ERR_UNSUPPORTED, "more than 2^31 chunk draws in one call");
-            const dim3 grid(launch_cap(c, ((int64_t)k.b.n_chunks * Dres + 63) / 64)), block(64);
-            hipLaunchKernelGGL(resolve_reg8_kernel, grid, block, 0, rs, k, Dres);
-        } else {
-            const dim3 grid(launch_cap(c, k.b.n_chunks)), block(64);
-            hipLaunchKernelGGL(resolve_reg_kernel, grid, block, 0, rs, k);
-        }
-        HIPCHK(hipGetLastError());
-        return LSLAM_OK;
-    }
-    static std::once_flag once;
-    std::call_once(once, [] {
-        set_max_lds(resolve_kernel<uint8_t>);
-        set_max_lds(resolve_kernel<uint16_t>);
-    });
-    const dim3 grid(launch_cap(c, k.b.n_chunks)), block(64);
-    if (k.j8) hipLaunchKernelGGL(resolve_kernel<uint8_t>, grid, block, lds, rs, k);
-    else hipLaunchKernelGGL(resolve_kernel<uint16_t>, grid, block, lds, rs, k);
-    HIPCHK(hipGetLastError());
-    return LSLAM_OK;
-}
-
-// Fresh streams (np.random.seed per scan, no mt_state_in): seed_kernel fills a seed buffer and
-// k.seed_state points the producer at it.  In the pipeline (on_side) it runs on its own stream
-// as soon as the call is enqueued -- after the input waits the producer would make (copies into
-// the seeds, a previous call writing them) and after the producer that last read its buffer
-// (two buffers by call parity) -- so it overlaps the previous call's producer, and the producer
-// only waits for its event.  Measured and dropped: seed_kernel in the producer's stream order,
-// right before rng_kernel (every producer launch 40 us later, moved onto the next resolve's
-// launch: 0.917 vs 0.715 ms per C3 step) or before its slot wait (0.786 vs 0.716 ms: the
-// producers no longer run back to back).  Returns the buffer index used (-1: none).
-static int launch_seed(lslam_ctx *c, KArgs &k, hipStream_t stream, bool on_side, bool wait_copy, bool wait_call,
-                       int &buf) {
-    k.seed_state = nullptr;
-    buf = -1;
-    if (k.b.mt_state_in || k.b.n_scans <= 0) return LSLAM_OK;
-    const int i = on_side ? c->seed_next : 2;
-    const size_t need = (size_t)k.b.n_scans * MT_N * 4;
-    if (c->seedst_bytes[i] < need) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        HIPCHK(hipStreamSynchronize(c->pstream));
-        HIPCHK(hipStreamSynchronize(c->sstream));
-        if (c->seedst[i]) HIPCHK(hipFree(c->seedst[i]));
-        c->seedst[i] = nullptr;
-        c->seedst_bytes[i] = 0;
-        hipError_t e = hipMalloc(&c->seedst[i], need);
-        if (e == hipErrorOutOfMemory) return set_err(LSLAM_ERR_NOMEM, "hipMalloc: out of memory (seed states)");
-        HIPCHK(e);
-        c->seedst_bytes[i] = need;
-    }
-    hipStream_t ss = stream;
-    if (on_side) {
-        ss = c->sstream;
-        HIPCHK(hipStreamWaitEvent(ss, c->ev_seed_read[i], 0));
-        if (wait_copy) HIPCHK(hipStreamWaitEvent(ss, c->ev_copy, 0));
-        if (wait_call) HIPCHK(hipStreamWaitEvent(ss, c->ev_call, 0));
-    }
-    hipLaunchKernelGGL(seed_kernel, dim3((unsigned)((k.b.n_scans + 63) / 64)), dim3(64), 0, ss, k.b.seeds,
-                       (int)k.b.n_scans, c->seedst[i]);
-    HIPCHK(hipGetLastError());
-    k.cuts = nullptr;
-    if (on_side && k.b.n_chunks > 0 && k.b.max_chunk_points <= 128) {  // chunk_kernel's chunks
-        const int j = c->cut_next;
-        const size_t cneed = (size_t)k.b.n_chunks * sizeof(ChunkCut);
-        if (c->cutb_bytes[j] < cneed) {
-            HIPCHK(hipStreamSynchronize(c->stream));
-            HIPCHK(hipStreamSynchronize(c->pstream));
-            HIPCHK(hipStreamSynchronize(c->sstream));
-            if (c->cutb[j]) HIPCHK(hipFree(c->cutb[j]));
-            c->cutb[j] = nullptr;
-            c->cutb_bytes[j] = 0;
-            hipError_t e = hipMalloc(&c->cutb[j], cneed);
-            if (e == hipErrorOutOfMemory) return set_err(LSLAM_ERR_NOMEM, "hipMalloc: out of memory (chunk cutoffs)");
-            HIPCHK(e);
-            c->cutb_bytes[j] = cneed;
-        }
-        hipLaunchKernelGGL(cut_lane_kernel, dim3((unsigned)((k.b.n_chunks + 63) / 64)), dim3(64), 0, ss, k, c->cutb[j]);
-        HIPCHK(hipGetLastError());
-        k.cuts = c->cutb[j];
-        c->cut_next = (j + 1) & 3;
-    }
-    if (on_side) {
-        HIPCHK(hipEventRecord(c->ev_seeded[i], ss));
-        HIPCHK(hipStreamWaitEvent(stream, c->ev_seeded[i], 0));
-        c->seed_next ^= 1;
-    }
-    k.seed_state = c->seedst[i];
-    buf = on_side ? i : -1;
-    return LSLAM_OK;
-}
-
-static int launch_rng(lslam_ctx *c, const KArgs &base, hipStream_t stream) {
-    KArgs k = base;
-    k.rt_all = c->rt_all;
-    if (k.b.mt_state_in || k.ep_d0 != 0) k.seed_state = nullptr;  // a chained state, or a later epoch
-    int lds = 0;
-    int st = layout_rng(k, &k.b, lds);
-    if (st) return st;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        set_max_lds(rng_kernel<uint8_t>);
-        set_max_lds(rng_kernel<uint16_t>);
-    });
-    st = timer_begin(c, LSLAM_K_RNG, stream);
-    if (st) return st;
-    const dim3 grid((unsigned)((k.b.n_scans + RNG_PPW - 1) / RNG_PPW)), block(64 * RNG_PPW);
-    if (k.j8) hipLaunchKernelGGL((rng_kernel<uint8_t>), grid, block, lds, stream, k);
-    else hipLaunchKernelGGL((rng_kernel<uint16_t>), grid, block, lds, stream, k);
-    HIPCHK(hipGetLastError());
-    return timer_end(c, LSLAM_K_RNG, stream);
-}
-
-// Producer + resolve of a call: one launch, or k.ep_count epochs in alternating
-// slots (prepare_steps).  rng_kernel runs on `ps` (after the previous epoch's
-// resolve released its slot), the resolve on the ctx stream.  final_out: where
-// the last launch writes the end state (null: the slot's state area).  On return
-// k.state_scr is the end state's area and last_slot the slot the caller releases.
-static int produce_draws(lslam_ctx *c, KArgs &k, int slot, hipStream_t ps, uint32_t *final_out, int &last_slot) {
-    const int D = k.T + 1;
-    // An epoch's resolve (the lane walk on a grid of two waves per SIMD) runs on the ctx
-    // stream beside the next epoch's producer on ps, the slots alternating (C5: 78 vs 89 ms
-    // per call with the epochs one after the other).
-    const uint32_t *prev_state = nullptr;
-    int sl = slot;
-    for (int e = 0; e < k.ep_count; e++) {
-        KArgs ke = k;
-        if (k.ep_count > 1) {
-            ke.ep_d0 = e * k.ep_nd;
-            ke.ep_nd = std::min(k.ep_nd, D - ke.ep_d0);
-            ke.jbuf = (unsigned char *)c->pslot[sl] + JBUF_FRONT;
-            ke.state_scr = (uint32_t *)((unsigned char *)c->pslot[sl] + k.slot_jbytes);
-            if (e > 0) {
-                if (ps != c->stream) HIPCHK(hipStreamWaitEvent(ps, c->ev_slot_free[sl], 0));
-                ke.b.mt_state_in = prev_state;  // the previous epoch's end state (same parser, draw boundary)
-            }
-        }
-        const bool last = e == k.ep_count - 1;
-        ke.b.mt_state_out = (last && final_out) ? final_out : ke.state_scr;
-        int st = launch_rng(c, ke, ps);
-        if (st) return st;
-        if (ps != c->stream) {
-            HIPCHK(hipEventRecord(c->ev_produced, ps));
-            HIPCHK(hipStreamWaitEvent(c->stream, c->ev_produced, 0));
-        }
-        st = launch_resolve(c, ke, c->stream);
-        if (st) return st;
-        if (!last) HIPCHK(hipEventRecord(c->ev_slot_free[sl], c->stream));
-        prev_state = ke.state_scr;
-        last_slot = sl;
-        sl = (sl + 1) % NSLOTS;
-    }
-    k.state_scr = const_cast<uint32_t *>(prev_state);
-    c->next_slot = sl;
-    return LSLAM_OK;
-}
-
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    if (!a || !b || !na || !nb) return false;
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
-// did a copy since the producer last synchronised with ev_copy write [p, p + n)?
-static bool copy_unknown_or_hits(const lslam_ctx *c, const void *p, size_t n) {
-    if (c->copy_unknown) return true;
-    for (int j = 0; j < c->n_copy_rng; j++)
-        if (ranges_overlap(p, n, c->copy_rng[j].p, c->copy_rng[j].n)) return true;
-    return false;
-}
-
-// did a copy since the producer last synchronised with ev_copy write one of its inputs?
-static bool copy_hazard(const lslam_ctx *c, const lslam_scan_batch *b) {
-    if (c->copy_unknown) return true;
-    const void *in[4] = {b->seeds, b->scan_chunk_off, b->chunk_pt_off, b->mt_state_in};
-    const size_t len[4] = {(size_t)b->n_scans * 4, (size_t)(b->n_scans + 1) * 4, (size_t)(b->n_chunks + 1) * 4,
-                           (size_t)b->n_scans * 625 * 4};
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < c->n_copy_rng; j++)
-            if (ranges_overlap(in[i], len[i], c->copy_rng[j].p, c->copy_rng[j].n)) return true;
-    return false;
-}
-
-// does the producer of this call read anything the previous pipeline call wrote?
-// 0: no; 1: only the previous call's mt_state_out (final once that call's fix-up ran:
-// a chained stream, e.g. LandmarkMap steps); 2: something else (wait for the whole call)
-static int producer_hazard(const lslam_ctx *c, const lslam_scan_batch *b) {
-    if (c->out_unknown) return 2;
-    const void *in[4] = {b->seeds, b->scan_chunk_off, b->chunk_pt_off, b->mt_state_in};
-    const size_t len[4] = {(size_t)b->n_scans * 4, (size_t)(b->n_scans + 1) * 4, (size_t)(b->n_chunks + 1) * 4,
-                           (size_t)b->n_scans * 625 * 4};
-    int level = 0;
-    for (int i = 0; i < 4; i++)
-        for (int j = 0; j < c->n_out; j++)
-            if (ranges_overlap(in[i], len[i], c->out_ptr[j], c->out_len[j]))
-                level = max(level, (i == 3 && c->out_ptr[j] == c->prev_state_out && c->prev_fixed) ? 1 : 2);
-    return level;
-}
-
-// add [p, p + n) to the union of buffers written since the producer last waited for ev_call
-static void note_out(lslam_ctx *c, const void *p, size_t n) {
-    if (!p || !n) return;
-    for (int i = 0; i < c->n_out; i++)
-        if (c->out_ptr[i] == p && c->out_len[i] == n) return;
-    if (c->n_out == LSLAM_MAX_OUTS) {
-        c->out_unknown = 1;
-        return;
-    }
-    c->out_ptr[c->n_out] = p;
-    c->out_len[c->n_out] = n;
-    c->n_out++;
-}
-
-static void remember_outputs(lslam_ctx *c, const lslam_scan_batch *b, int T, int L) {
-    const size_t S = (size_t)b->n_scans, C = (size_t)b->n_chunks, P = (size_t)b->n_points;
-    const void *p[11] = {b->inlier_mask, b->models, b->y_proj, b->draws_out, b->trial_cnt_out, b->mt_state_out,
-                         b->landmarks, b->lmk_count, b->lmk_walk, b->ukf_x, b->ukf_P};
-    const size_t n[11] = {P, C * sizeof(lslam_chunk_model), P * 8, C * 2 * (T + 1) * 4, C * T * 4, S * 625 * 4,
-                          S * b->lmk_capacity * sizeof(lslam_landmark), S * 4, S * b->lmk_capacity * 4,
-                          L ? S * 24 : 0, L ? S * 72 : 0};
-    for (int i = 0; i < 11; i++) note_out(c, p[i], n[i]);
-}
-
-// Every entry point that enqueues device work ends here.  Each call's work on the producer
-// and side streams joins the ctx stream before the call returns, so "every call so far" is the
-// ctx stream's tail: copies on the ctx stream follow it by stream order, and another stream
-// that must wait for it records ev_call at that moment (mark_calls) and waits on that.  An
-// event recorded at every call's end would be a marker packet inside the pipelined ctx chain
-// (~7 us between two kernels on the MI355X).
-static int end_call(lslam_ctx *c) {
-    (void)c;
-    return LSLAM_OK;
-}
-static int mark_calls(lslam_ctx *c) {
-    HIPCHK(hipEventRecord(c->ev_call, c->stream));
-    return LSLAM_OK;
-}
-
-// select_kernel LDS: the chunk's points, tied trials, tie sums, mask, sum scratch
-static int layout_select(KArgs &k, const lslam_scan_batch *b, int &lds) {
-    const int N = b->max_chunk_points > 0 ? b->max_chunk_points : 1;
-    const int T = k.T > 0 ? k.T : 1;
-    int off = 0;
-    k.off_pts = off; off += align16(16 * N);
-    k.off_tied = off; off += align16(4 * T);
-    k.off_cnt = off; off += align16(4 * T);
-    k.off_tsum = off; off += align16(8 * T);
-    k.off_mask = off; off += align16(N);
-    k.off_vstack = off; off += align16(8 * 24);
-    k.off_nstack = off; off += align16(4 * 72);
-    k.off_vtmp = off; off += align16(8 * 128);
-    lds = off;
-    if (lds > 160 * 1024) return set_err(LSLAM_ERR_CAPACITY, "chunk/trial sizes exceed the 160 KiB LDS");
-    return LSLAM_OK;
-}
-
-static int ensure_cscr(lslam_ctx *c, size_t bytes) {
-    if (c->cscr_bytes >= bytes) return LSLAM_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->cscr) HIPCHK(hipFree(c->cscr));
-    c->cscr = nullptr;
-    c->cscr_bytes = 0;
-    hipError_t e = hipMalloc(&c->cscr, bytes);
-    if (e == hipErrorOutOfMemory) return set_err(LSLAM_ERR_NOMEM, "hipMalloc: out of memory (consensus scratch)");
-    HIPCHK(e);
-    c->cscr_bytes = bytes;
-    return LSLAM_OK;
-}
-
-// chunks of more than 128 points: count_kernel (many waves per chunk) + select_kernel
-static int launch_chunks_large(lslam_ctx *c, KArgs &k) {
-    const int T = k.T;
-    const size_t nc = (size_t)k.b.n_chunks;
-    const size_t cnt_bytes = (k.b.trial_cnt_out || T == 0) ? 0 : ((nc * T * 4 + 255) & ~(size_t)255);
-    const bool philox = k.hyp_source == LSLAM_HYP_PHILOX;
-    const size_t drw_bytes = (philox && !k.b.draws_out) ? ((nc * 2 * (size_t)(T + 1) * 4 + 255) & ~(size_t)255) : 0;
-    const size_t mdl_bytes = nc * (size_t)(T > 0 ? T : 1) * 32;
-    int st = ensure_cscr(c, cnt_bytes + drw_bytes + mdl_bytes);
-    if (st) return st;
-    unsigned char *base = (unsigned char *)c->cscr;
-    k.cnt_scr = k.b.trial_cnt_out ? k.b.trial_cnt_out : (int32_t *)base;
-    if (philox) k.draws_scr = k.b.draws_out ? k.b.draws_out : (int32_t *)(base + cnt_bytes);
-    k.models = (double *)(base + cnt_bytes + drw_bytes);
-    const int N = k.b.max_chunk_points;
-    int lds_sel = 0;
-    st = layout_select(k, &k.b, lds_sel);
-    if (st) return st;
-    k.cnt_blocks = T > 0 ? (T + CNT_HYP_BLOCK - 1) / CNT_HYP_BLOCK : 0;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        set_max_lds(select_kernel<LSLAM_HYP_MT19937>);
-        set_max_lds(select_kernel<LSLAM_HYP_PHILOX>);
-        set_max_lds(select_kernel<LSLAM_HYP_EXPLICIT>);
-    });
-    const size_t nmod = nc * (size_t)(T + 1);
-    const dim3 mgrid((unsigned)((nmod + 255) / 256)), block(256);
-    switch (k.hyp_source) {
-        case LSLAM_HYP_PHILOX: hipLaunchKernelGGL(model_kernel<LSLAM_HYP_PHILOX>, mgrid, block, 0, c->stream, k); break;
-        case LSLAM_HYP_EXPLICIT: hipLaunchKernelGGL(model_kernel<LSLAM_HYP_EXPLICIT>, mgrid, block, 0, c->stream, k); break;
-        default: hipLaunchKernelGGL(model_kernel<LSLAM_HYP_MT19937>, mgrid, block, 0, c->stream, k); break;
-    }
-    HIPCHK(hipGetLastError());
-    if (k.cnt_blocks > 0) {
-        const dim3 grid((unsigned)(nc * k.cnt_blocks)), cblock(CNT_TPB);
-        // points per lane: the smallest power of two covering the chunk, at most 16 (then tiles)
-        if (N <= 256) hipLaunchKernelGGL(count_kernel<1>, grid, cblock, 0, c->stream, k);
-        else if (N <= 512) hipLaunchKernelGGL(count_kernel<2>, grid, cblock, 0, c->stream, k);
-        else if (N <= 1024) hipLaunchKernelGGL(count_kernel<4>, grid, cblock, 0, c->stream, k);
-        else if (N <= 2048) hipLaunchKernelGGL(count_kernel<8>, grid, cblock, 0, c->stream, k);
-        else hipLaunchKernelGGL(count_kernel<16>, grid, cblock, 0, c->stream, k);
-        HIPCHK(hipGetLastError());
-    }
-    const dim3 grid((unsigned)nc), sblock(64);
-    switch (k.hyp_source) {
-        case LSLAM_HYP_PHILOX: hipLaunchKernelGGL(select_kernel<LSLAM_HYP_PHILOX>, grid, sblock, lds_sel, c->stream, k); break;
-        case LSLAM_HYP_EXPLICIT: hipLaunchKernelGGL(select_kernel<LSLAM_HYP_EXPLICIT>, grid, sblock, lds_sel, c->stream, k); break;
-        default: hipLaunchKernelGGL(select_kernel<LSLAM_HYP_MT19937>, grid, sblock, lds_sel, c->stream, k); break;
-    }
-    HIPCHK(hipGetLastError());
-    return LSLAM_OK;
-}
-
-static int launch_chunks(lslam_ctx *c, const KArgs &base, bool write_yproj) {
-    if (base.b.n_chunks == 0) return LSLAM_OK;
-    KArgs k = base;
-    k.write_yproj = write_yproj ? 1 : 0;
-    int st = timer_begin(c, LSLAM_K_CONSENSUS);
-    if (st) return st;
-    if (k.b.max_chunk_points > 128) {
-        st = launch_chunks_large(c, k);
-        if (st) return st;
-        return timer_end(c, LSLAM_K_CONSENSUS);
-    }
-    int lds = 0;
-    st = layout_chunk(k, &k.b, lds);
-    if (st) return st;
-    static std::once_flag once;
-    std::call_once(once, [] {
-        set_max_lds(chunk_kernel<LSLAM_HYP_MT19937>);
-        set_max_lds(chunk_kernel<LSLAM_HYP_PHILOX>);
-        set_max_lds(chunk_kernel<LSLAM_HYP_EXPLICIT>);
-    });
-    const dim3 grid(launch_cap(c, k.b.n_chunks)), block(64);
-    switch (k.hyp_source) {
-        case LSLAM_HYP_PHILOX: hipLaunchKernelGGL(chunk_kernel<LSLAM_HYP_PHILOX>, grid, block, lds, c->stream, k); break;
-        case LSLAM_HYP_EXPLICIT: hipLaunchKernelGGL(chunk_kernel<LSLAM_HYP_EXPLICIT>, grid, block, lds, c->stream, k); break;
-        default: hipLaunchKernelGGL(chunk_kernel<LSLAM_HYP_MT19937>, grid, block, lds, c->stream, k); break;
-    }
-    HIPCHK(hipGetLastError());
-    return timer_end(c, LSLAM_K_CONSENSUS);
-}
-
-template <int MODE>
-static int launch_post(lslam_ctx *c, const KArgs &k, int lds) {
-    static std::once_flag once;
-    std::call_once(once, [] {
-        set_max_lds(scan_kernel<LSLAM_HYP_EXPLICIT, MODE>);
-        set_max_lds(scan_kernel_w4<LSLAM_HYP_EXPLICIT, MODE>);
-    });
-    const dim3 grid(launch_cap(c, k.b.n_scans));
-    if (MODE == MODE_ASSOC && k.lmk_reg) {
-        static std::once_flag once_reg;
-        std::call_once(once_reg, [] { set_max_lds(post_reg_kernel); });
-        hipLaunchKernelGGL(post_reg_kernel, grid, dim3(64), lds, c->stream, k);
-    } else if (k.hyp_source == LSLAM_HYP_MT19937)  // beside the next call's producer
-        hipLaunchKernelGGL((scan_kernel<LSLAM_HYP_EXPLICIT, MODE>), grid, dim3(64), lds, c->stream, k);
-    else
-        hipLaunchKernelGGL((scan_kernel_w4<LSLAM_HYP_EXPLICIT, MODE>), grid, dim3(64), lds, c->stream, k);
-    HIPCHK(hipGetLastError());
-    return LSLAM_OK;
-}
-
-// rng_kernel -> chunk_kernel -> fix-up -> association/UKF post pass, all on the ctx stream
-static int run_split(lslam_ctx *c, const lslam_scan_batch *b, const lslam_ransac_params *p,
-                     const lslam_ukf_params *u) {
-    HIPCHK(hipSetDevice(c->device));
-    if (b->n_scans == 0) return LSLAM_OK;
-#if defined(LSLAM_STAMPS) || defined(LSLAM_CENSUS)
-    g_call_seq += 1;
-#endif
-    const bool assoc = b->landmarks != nullptr;
-    KArgs k;
-    int lds_fix = 0;
-    int st = build_args(k, b, p, nullptr, MODE_RANSAC, lds_fix);
-    if (st) return st;
-    const bool mt = k.hyp_source == LSLAM_HYP_MT19937;
-    bool spec = false;
-    int seed_buf = -1;  // the seed buffer this call's producer reads (launch_seed)
-    int slot = c->next_slot;
-    if (mt) {
-        st = prepare_steps(c, k, slot);
-        if (st) return st;
-        c->next_slot = (c->next_slot + 1) % NSLOTS;
-    }
-    KArgs kp;
-    int lds_post = 0;
-    // a UKF step that reads nothing of this call's RANSAC (no LMK_FROM_RANSAC / MAP) runs
-    // on the side stream, off the resolve -> consensus -> association chain
-    // (Philox / explicit hypotheses only: beside the MT producer a third stream of UKF waves
-    // slows the resolve -> consensus chain more than it saves, 1.23 -> 1.27-1.32 ms on C3, and
-    // made the step bimodal)
-    const bool ukf_side = p->hyp_source != LSLAM_HYP_MT19937 && u &&
-                          !(u->flags & (LSLAM_UKF_LMK_FROM_RANSAC | LSLAM_UKF_MAP));
-    // the UKF of the fused call on lane groups after the association pass (not in MAP mode,
-    // whose measurements come out of the association walk itself)
-    const bool ukf_lane = u && !ukf_side && !(u->flags & LSLAM_UKF_MAP);
-    const int pmode = (assoc ? MODE_ASSOC : MODE_POST) | (u && !ukf_side && !ukf_lane ? MODE_UKF : 0);
-    if ((pmode & MODE_UKF) && !(u->flags & LSLAM_UKF_MAP))  // scan_body's one-wave UKF fuses no origins
-        return set_err(LSLAM_ERR_UNSUPPORTED, "post pass given a non-map UKF step");
-    if (assoc || (u && !ukf_side && !ukf_lane)) {
-        st = build_args(kp, b, p, (ukf_side || ukf_lane) ? nullptr : u, pmode, lds_post);
-        if (st) return st;
-    }
-    KArgs kl;
-    if (ukf_lane) {
-        int lds_l = 0;
-        st = build_args(kl, b, p, u, MODE_UKF, lds_l);
-        if (st) return st;
-        if ((u->flags & LSLAM_UKF_LMK_FROM_RANSAC) && !b->models)
-            return set_err(LSLAM_ERR_ARG, "LSLAM_UKF_LMK_FROM_RANSAC needs the chunk models");
-    }
-    KArgs ku;
-    int lds_u = 0;
-    if (ukf_side) {
-        st = build_args(ku, b, nullptr, u, MODE_UKF, lds_u);
-        if (st) return st;
-    }
-    st = timer_begin(c, LSLAM_K_PIPELINE);
-    if (st) return st;
-    if (ukf_side) {
-        // after the previous call (its outputs may be this step's inputs) and the latest copies
-        if ((st = mark_calls(c))) return st;
-        HIPCHK(hipStreamWaitEvent(c->ustream, c->ev_call, 0));
-        HIPCHK(hipStreamWaitEvent(c->ustream, c->ev_copy, 0));
-        launch_ukf_group(ku, u->n_landmarks, c->ustream, false);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(c->ev_ukf, c->ustream));
-    }
-    if (mt) {
-        // producer on its own stream: it waits for input copies, (on a hazard) for the previous
-        // call, and for its slot's previous consumers; the consumers wait for it.  A fresh
-        // stream's seed_kernel goes between the input waits and the slot wait (launch_seed).
-        // a copy into this call's MT state (e.g. a caller's upload into the previous call's
-        // mt_state_out) invalidates speculating from the previous producer's end state
-        const bool state_copied = copy_unknown_or_hits(c, b->mt_state_in, (size_t)b->n_scans * 625 * 4);
-        const bool chz = copy_hazard(c, b);
-        if (chz) {
-            HIPCHK(hipStreamWaitEvent(c->pstream, c->ev_copy, 0));
-            c->n_copy_rng = 0;
-            c->copy_unknown = 0;
-        }
-        const int hz = producer_hazard(c, b);
-        if (hz == 2) {
-            // ev_call follows every call enqueued so far: the union starts afresh
-            if ((st = mark_calls(c))) return st;
-            HIPCHK(hipStreamWaitEvent(c->pstream, c->ev_call, 0));
-            c->n_out = 0;
-            c->out_unknown = 0;
-        }
-        if ((st = launch_seed(c, k, c->pstream, true, chz, hz == 2, seed_buf))) return st;
-        HIPCHK(hipStreamWaitEvent(c->pstream, c->ev_slot_free[slot], 0));
-        // speculation (a chained stream, e.g. LandmarkMap steps): parse from the previous
-        // producer's end state, which precedes this producer on pstream, instead of waiting for
-        // the previous fix-up; this call's fix-up replays the scans that one replayed
-        spec = hz == 1 && c->speculate && c->spec_ok && k.ep_count == 1 && c->prev_state_scr &&
-               c->prev_spec_scans == b->n_scans && b->mt_state_in == c->prev_state_out && !state_copied;
-        // a scan replayed by a speculative call stays dirty in every later one (its producer state
-        // is never repaired): every SPEC_RESYNC-th chained call waits for the
-        // previous fix-up instead, which clears the flags (test_gpu_speculate.py runs past it)
-        constexpr int SPEC_RESYNC = 32;
-        if (spec && ++c->spec_run >= SPEC_RESYNC) spec = false;
-        if (!spec) c->spec_run = 0;
-        if (hz == 1 && !spec) HIPCHK(hipStreamWaitEvent(c->pstream, c->ev_slot_free[c->prev_slot], 0));
-        // a producer that waited on the previous call will most likely wait on this one too, so
-        // this call's resolve runs alone: the LDS-staged form is faster there (map mode 1.48 vs
-        // 1.39 ms per step); otherwise the next call's producer runs beside it and holds the LDS
-        // (C3 0.93 vs 1.03 ms)
-        c->resolve_beside = hz == 0 || spec;
-        const uint32_t *true_in = k.b.mt_state_in;
-        if (spec) k.b.mt_state_in = c->prev_state_scr;
-        st = produce_draws(c, k, slot, c->pstream, nullptr, slot);  // slot <- the last epoch's
-        k.b.mt_state_in = true_in;  // the fix-up's replays start from the true state
-        if (st) return st;
-        if (seed_buf >= 0) HIPCHK(hipEventRecord(c->ev_seed_read[seed_buf], c->pstream));
-    }
-    // A UKF that reads nothing of this call's RANSAC runs between the fix-up and the post pass.
-    // The fix-up releases this call's steps slot; the next producer starts ~40 us after that
-    // event, so a UKF placed right behind the fix-up runs alone (35 us) instead of beside the
-    // parsers (~180 us): C3 0.893 -> 0.858 ms per step, the producer 0.79 -> 0.71 ms in the
-    // pipeline.  (Measured and dropped, DESIGN.md §8: the UKF before the fix-up, +2.7 %, or
-    // before the consensus, +0.8 %; the slot released after the post pass or at the call's end.)
-    const bool ukf_indep = ukf_lane && !(u->flags & (LSLAM_UKF_LMK_FROM_RANSAC | LSLAM_UKF_MAP));
-    st = launch_chunks(c, k, !assoc);
-    if (st) return st;
-    if (mt) {
-        KArgs kf = k;
-        kf.fixup = 1;
-        // replay flags: this call's, for the next call's speculation (one epoch only: the
-        // end state is then the slot's state area)
-        if (k.ep_count == 1 && b->mt_state_out) {
-            if (c->spec_dirty_n < b->n_scans) {
-                HIPCHK(hipStreamSynchronize(c->stream));
-                for (int i = 0; i < 2; i++) {
-                    if (c->spec_dirty[i]) HIPCHK(hipFree(c->spec_dirty[i]));
-                    c->spec_dirty[i] = nullptr;
-                }
-                c->spec_dirty_n = 0;
-                for (int i = 0; i < 2; i++) {
-                    hipError_t e = hipMalloc(&c->spec_dirty[i], (size_t)b->n_scans);
-                    if (e == hipErrorOutOfMemory) return set_err(LSLAM_ERR_NOMEM, "hipMalloc: out of memory (flags)");
-                    HIPCHK(e);
-                }
-                c->spec_dirty_n = b->n_scans;
-                if (spec) return set_err(LSLAM_ERR_HIP, "speculation without replay flags");  // unreachable
-            }
-            kf.spec_dirty_in = spec ? c->spec_dirty[c->spec_cur] : nullptr;
-            kf.spec_dirty_out = c->spec_dirty[c->spec_cur ^ 1];
-        }
-        static std::once_flag once;
-        std::call_once(once, [] { set_max_lds(scan_kernel<LSLAM_HYP_MT19937, MODE_RANSAC>); });
-        hipLaunchKernelGGL((scan_kernel<LSLAM_HYP_MT19937, MODE_RANSAC>), dim3(launch_cap(c, b->n_scans)), dim3(64), lds_fix,
-                           c->stream, kf);
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipEventRecord(c->ev_slot_free[slot], c->stream));
-    }
-    if (ukf_indep) {
-        launch_ukf_group(kl, u->n_landmarks, c->stream, true);
-        HIPCHK(hipGetLastError());
-    }
-    // (mt_state_out is final after the fix-up: the next call's producer may chain from it early)
-    c->prev_state_out = mt ? b->mt_state_out : nullptr;
-    c->prev_slot = slot;
-    c->prev_fixed = mt ? 1 : 0;
-    c->spec_ok = (mt && k.ep_count == 1 && b->mt_state_out) ? 1 : 0;
-    if (c->spec_ok) {
-        c->spec_cur ^= 1;  // the buffer this call's fix-up writes
-        c->prev_state_scr = k.state_scr;
-        c->prev_spec_scans = b->n_scans;
-    }
-    switch (pmode) {
-        case MODE_ASSOC | MODE_UKF: st = launch_post<MODE_ASSOC | MODE_UKF>(c, kp, lds_post); break;
-        case MODE_POST | MODE_UKF: st = launch_post<MODE_POST | MODE_UKF>(c, kp, lds_post); break;
-        case MODE_ASSOC: st = launch_post<MODE_ASSOC>(c, kp, lds_post); break;
-        default: break;
-    }
-    if (st) return st;
-    if (ukf_lane && !ukf_indep) {  // reads this call's chunk models (LMK_FROM_RANSAC)
-        launch_ukf_group(kl, u->n_landmarks, c->stream, true);
-        HIPCHK(hipGetLastError());
-    }
-    if (ukf_side) HIPCHK(hipStreamWaitEvent(c->stream, c->ev_ukf, 0));
-    remember_outputs(c, b, k.T, u ? u->n_landmarks : 0);
-    if ((st = end_call(c))) return st;
-    return timer_end(c, LSLAM_K_PIPELINE);
-}
-
-
-// ---- express-scan codec (lslam_express.h) ----
-
-static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static int ensure_escr(lslam_ctx *c, size_t bytes) {
-    if (c->escr_bytes >= bytes) return LSLAM_OK;
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (c->escr) HIPCHK(hipFree(c->escr));
-    c->escr = nullptr;
-    c->escr_bytes = 0;
-    hipError_t e = hipMalloc(&c->escr, bytes);
-    if (e == hipErrorOutOfMemory) return set_err(LSLAM_ERR_NOMEM, "hipMalloc: out of memory (express scratch)");
-    HIPCHK(e);
-    c->escr_bytes = bytes;
-    return LSLAM_OK;
-}
-
-// packet streams are read as dwords: 4-byte alignment, and every rank fits int32
-static int express_check(const uint8_t *packets, int64_t n) {
-    if (n < 0 || (n > 0 && !packets)) return set_err(LSLAM_ERR_ARG, "express: bad packet stream");
-    if (((uintptr_t)packets & 3) != 0) return set_err(LSLAM_ERR_ARG, "express: packet stream must be 4-byte aligned");
-    if (n > ((int64_t)1 << 26)) return set_err(LSLAM_ERR_ARG, "express: more than 2^26 packets per call");
-    return LSLAM_OK;
-}
-
-extern "C" {
-
-int lslam_polar_to_xy(lslam_ctx *c, const double *th, const double *d, double *xy, int64_t n) {
-    if (!c || n < 0 || (n > 0 && (!th || !d || !xy))) return LSLAM_ERR_ARG;
-    if (n == 0) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    int64_t blocks = (n + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    int st = timer_begin(c, LSLAM_K_POLAR);
-    if (st) return st;
-    hipLaunchKernelGGL(polar_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, th, d, (double2 *)xy, n);
-    HIPCHK(hipGetLastError());
-    st = timer_end(c, LSLAM_K_POLAR);
-    if (st) return st;
-    note_out(c, xy, (size_t)n * 16);
-    return end_call(c);
-}
-
-int lslam_set_steps_budget(lslam_ctx *c, int64_t bytes) {
-    if (!c) return LSLAM_ERR_ARG;
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamSynchronize(c->pstream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->steps_budget = bytes > 0 ? (size_t)bytes : default_steps_budget();
-    return LSLAM_OK;
-}
-
-int lslam_hyp_mt19937(lslam_ctx *c, const lslam_scan_batch *b, int32_t max_trials) {
-    if (!c) return LSLAM_ERR_ARG;
-    int st = validate_batch(b, false);
-    if (st) return st;
-    if (!b->draws_out) return set_err(LSLAM_ERR_ARG, "draws_out required");
-    lslam_ransac_params p;
-    lslam_ransac_params_default(&p);
-    p.max_trials = max_trials;
-    KArgs k;
-    int lds = 0;
-    st = build_args(k, b, &p, nullptr, MODE_HYP_ONLY, lds);
-    if (st) return st;
-    HIPCHK(hipSetDevice(c->device));
-    if (b->n_scans == 0) return LSLAM_OK;
-    k.hyp_source = LSLAM_HYP_MT19937;
-    const int slot = c->next_slot;
-    st = prepare_steps(c, k, slot);
-    if (st) return st;
-    c->next_slot = (c->next_slot + 1) % NSLOTS;
-    st = timer_begin(c, LSLAM_K_HYP);
-    if (st) return st;
-    HIPCHK(hipStreamWaitEvent(c->stream, c->ev_slot_free[slot], 0));
-    int last = slot;
-    // on the main stream; the end state goes straight to mt_state_out
-    c->resolve_beside = 0;  // alone on the ctx stream
-    int seed_buf = -1;
-    if ((st = launch_seed(c, k, c->stream, false, false, false, seed_buf))) return st;
-    st = produce_draws(c, k, slot, c->stream, b->mt_state_out, last);
-    if (st) return st;
-    HIPCHK(hipEventRecord(c->ev_slot_free[last], c->stream));
-    // the end state is written by the rng kernel itself, final at ev_slot_free[slot]: a
-    // pipeline call chaining from it waits for that event, anything else for ev_call
-    note_out(c, b->draws_out, (size_t)b->n_chunks * 2 * (size_t)(max_trials + 1) * 4);
-    note_out(c, b->mt_state_out, (size_t)b->n_scans * 625 * 4);
-    c->prev_state_out = b->mt_state_out;
-    c->prev_slot = last;
-    c->prev_fixed = b->mt_state_out ? 1 : 0;
-    c->spec_ok = 0;
-    c->spec_run = 0;
-    if ((st = end_call(c))) return st;
-    return timer_end(c, LSLAM_K_HYP);
-}
-
-int lslam_ransac(lslam_ctx *c, const lslam_scan_batch *b, const lslam_ransac_params *p) {
-    if (!c || !p) return LSLAM_ERR_ARG;
-    int st = validate_batch(b, true);
-    if (st) return st;
-    return run_split(c, b, p, nullptr);
-}
-
-int lslam_landmarks(lslam_ctx *c, const lslam_scan_batch *b, const lslam_ransac_params *p) {
-    if (!c || !p) return LSLAM_ERR_ARG;
-    int st = validate_batch(b, true);
-    if (st) return st;
-    if (!b->models || !b->landmarks || !b->inlier_mask) return set_err(LSLAM_ERR_ARG, "models/landmarks/mask required");
-    KArgs k;
-    int lds = 0;
-    st = build_args(k, b, p, nullptr, MODE_ASSOC, lds);
-    if (st) return st;
-    if ((st = run_scan_kernel<MODE_ASSOC>(c, k, lds, LSLAM_K_LANDMARK))) return st;
-    remember_outputs(c, b, k.T, 0);
-    return end_call(c);
-}
-
-static int ukf_step_impl(lslam_ctx *c, const lslam_scan_batch *b, const lslam_ukf_params *u, double *trace) {
-    if (!c || !u || !b) return LSLAM_ERR_ARG;
-    if (b->n_scans < 0) return LSLAM_ERR_ARG;
-    lslam_scan_batch bb = *b;
-    // UKF-only: no chunks are touched; give the kernel an empty CSR if absent
-    KArgs k;
-    int lds = 0;
-    if (!bb.scan_chunk_off) return set_err(LSLAM_ERR_ARG, "scan_chunk_off required (may describe 0 chunks)");
-    int st = build_args(k, &bb, nullptr, u, MODE_UKF, lds);
-    if (st) return st;
-    const bool lanes = !(u->flags & LSLAM_UKF_MAP);  // MAP: the one-wave form (its post pass's step)
-    if ((u->flags & LSLAM_UKF_SIGMAS_IN) && !b->ukf_sigmas)
-        return set_err(LSLAM_ERR_ARG, "LSLAM_UKF_SIGMAS_IN without ukf_sigmas");
-    if ((b->ukf_sigmas || trace) && !lanes)
-        return set_err(LSLAM_ERR_UNSUPPORTED, "ukf_sigmas / trace need the lane-group UKF (not LSLAM_UKF_MAP)");
-    if (trace && !(u->flags & LSLAM_UKF_UPDATE)) return set_err(LSLAM_ERR_ARG, "lslam_ukf_trace needs LSLAM_UKF_UPDATE");
-    if (trace || b->ukf_sigmas) {
-        HIPCHK(hipSetDevice(c->device));
-        if (k.b.n_scans > 0) {
-            if ((st = timer_begin(c, LSLAM_K_UKF))) return st;
-            launch_ukf_group(k, k.ukf.L, c->stream, false, trace);
-            HIPCHK(hipGetLastError());
-            if ((st = timer_end(c, LSLAM_K_UKF))) return st;
-        }
-    } else if ((st = run_scan_kernel<MODE_UKF>(c, k, lds, LSLAM_K_UKF))) {
-        return st;
-    }
-    note_out(c, b->ukf_x, (size_t)b->n_scans * 24);
-    note_out(c, b->ukf_P, (size_t)b->n_scans * 72);
-    if (b->ukf_sigmas) note_out(c, b->ukf_sigmas, (size_t)b->n_scans * 168);
-    if (trace) note_out(c, trace, (size_t)b->n_scans * 8 * ukf_tr_doubles(u->n_landmarks));
-    return end_call(c);
-}
-
-int lslam_ukf_step(lslam_ctx *c, const lslam_scan_batch *b, const lslam_ukf_params *u) {
-    return ukf_step_impl(c, b, u, nullptr);
-}
-
-int lslam_ukf_trace(lslam_ctx *c, const lslam_scan_batch *b, const lslam_ukf_params *u, double *trace) {
-    if (!trace) return set_err(LSLAM_ERR_ARG, "trace buffer required");
-    return ukf_step_impl(c, b, u, trace);
-}
-
-int lslam_scan_pipeline(lslam_ctx *c, const lslam_scan_batch *b, const lslam_ransac_params *p,
-                        const lslam_ukf_params *u) {
-    if (!c || !p) return LSLAM_ERR_ARG;
-    int st = validate_batch(b, true);
-    if (st) return st;
-    if (u && ((u->flags & LSLAM_UKF_SIGMAS_IN) || b->ukf_sigmas))
-        return set_err(LSLAM_ERR_UNSUPPORTED, "ukf_sigmas / LSLAM_UKF_SIGMAS_IN are lslam_ukf_step's (filterpy's cache)");
-    return run_split(c, b, p, u);
-}
-
-int lslam_express_decode(lslam_ctx *c, const uint8_t *packets, int64_t n_packets, const lslam_express_measures *out) {
-    if (!c || !out) return LSLAM_ERR_ARG;
-    int st = express_check(packets, n_packets);
-    if (st) return st;
-    if (n_packets == 0) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    ExpressOut o{out->angle_deg, out->dist_mm, out->new_scan, out->valid, (double2 *)out->xy, out->pkt_valid};
-    if ((st = timer_begin(c, LSLAM_K_EXPRESS))) return st;
-    const int64_t blocks = (n_packets + EXP_DEC_PER_WG - 1) / EXP_DEC_PER_WG;
-    hipLaunchKernelGGL(express_decode_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, packets, n_packets, o);
-    HIPCHK(hipGetLastError());
-    if ((st = timer_end(c, LSLAM_K_EXPRESS))) return st;
-    const size_t nm = (size_t)(n_packets > 1 ? n_packets - 1 : 0) * 32;
-    note_out(c, out->angle_deg, nm * 8);
-    note_out(c, out->dist_mm, nm * 8);
-    note_out(c, out->new_scan, nm);
-    note_out(c, out->valid, nm);
-    note_out(c, out->xy, nm * 16);
-    note_out(c, out->pkt_valid, (size_t)n_packets);
-    return end_call(c);
-}
-
-int lslam_express_scans(lslam_ctx *c, const uint8_t *packets, int64_t n_packets, int32_t skip,
-                        const lslam_express_revs *out) {
-    if (!c || !out || !out->counts || !out->scan_chunk_off || !out->chunk_pt_off) return LSLAM_ERR_ARG;
-    if (out->cap_scans < 0 || out->cap_chunks < 0 || out->cap_points < 0 || (out->cap_points > 0 && !out->xy))
-        return set_err(LSLAM_ERR_ARG, "express: bad output capacities");
-    int st = express_check(packets, n_packets);
-    if (st) return st;
-    if (skip < 0 || skip > 31) return set_err(LSLAM_ERR_ARG, "express: skip must be in [0, 31]");
-    HIPCHK(hipSetDevice(c->device));
-    const int64_t np = n_packets > 1 ? n_packets - 1 : 0;  // packets that carry measures
-    const int64_t tiles = (np + EXP_TILE - 1) / EXP_TILE;
-    size_t off = 0;
-    const size_t o_flags = off;
-    off = align256(off + (size_t)np);
-    const size_t o_tile = off;
-    off = align256(off + (size_t)tiles * sizeof(int2));
-    const size_t o_rank = off;
-    off = align256(off + (size_t)np * sizeof(int2));
-    const size_t o_rend = off;
-    off = align256(off + (size_t)np * sizeof(int2));
-    const size_t o_rinfo = off;
-    off = align256(off + (size_t)np * sizeof(int4));
-    if ((st = ensure_escr(c, off > 0 ? off : 256))) return st;
-    uint8_t *base = (uint8_t *)c->escr;
-    ExpressScratch s{base + o_flags, (int2 *)(base + o_tile), (int2 *)(base + o_rank), (int2 *)(base + o_rend),
-                     (int4 *)(base + o_rinfo), out->counts};
-    ExpressScans o{(double2 *)out->xy, out->scan_chunk_off, out->chunk_pt_off, out->cap_points, out->cap_scans,
-                   out->cap_chunks};
-    if ((st = timer_begin(c, LSLAM_K_EXPRESS))) return st;
-    if (tiles > 0) {
-        hipLaunchKernelGGL(express_flags_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, packets, n_packets,
-                           (int)skip, s);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(express_rank_kernel, dim3((unsigned)tiles), dim3(256), 0, c->stream, n_packets, (int)skip, s);
-        HIPCHK(hipGetLastError());
-    }
-    // revolutions <= packets with measures: one 256-revolution workgroup per packet tile
-    hipLaunchKernelGGL(express_revs_kernel, dim3((unsigned)(tiles > 0 ? tiles : 1)), dim3(256), 0, c->stream,
-                       (int)tiles, s, o);
-    HIPCHK(hipGetLastError());
-    if (np > 0) {
-        if ((st = timer_begin(c, LSLAM_K_EXPRESS_SCATTER))) return st;
-        const int64_t blocks = (np + EXP_DEC_PER_WG - 1) / EXP_DEC_PER_WG;
-        hipLaunchKernelGGL(express_scatter_kernel, dim3((unsigned)blocks), dim3(256), 0, c->stream, packets, n_packets,
-                           (int)skip, s, o);
-        HIPCHK(hipGetLastError());
-        if ((st = timer_end(c, LSLAM_K_EXPRESS_SCATTER))) return st;
-    }
-    if ((st = timer_end(c, LSLAM_K_EXPRESS))) return st;
-    // the outputs may feed a pipeline call whose MT producer runs on the other stream
-    HIPCHK(hipEventRecord(c->ev_copy, c->stream));
-    note_copy(c, out->xy, (size_t)out->cap_points * 16);
-    note_copy(c, out->scan_chunk_off, ((size_t)out->cap_scans + 1) * 4);
-    note_copy(c, out->chunk_pt_off, ((size_t)out->cap_chunks + 1) * 4);
-    note_copy(c, out->counts, 16);
-    return end_call(c);
-}
-
-}  // extern "C"
+#include "lslam_ctx.h"
+#include "lslam_launch.h"

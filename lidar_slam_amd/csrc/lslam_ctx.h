@@ -1,0 +1,501 @@
+// Host side, part 1 (included by lidarslam.hip after the kernels): the context -- streams, events,
+// timers, grow-only device buffers -- its create / destroy, and the small ABI utilities (version,
+// errors, memory, copies, timers, parameter defaults).  The launchers are in lslam_launch.h.
+#pragma once
+#include "lslam_hazards.h"
+
+constexpr int LSLAM_EV_RING = 64;
+constexpr int NSLOTS = 2;  // producer slots in the ring
+
+static thread_local std::string g_err;
+
+static size_t default_steps_budget() { return (size_t)2 << 30; }  // lslam_set_steps_budget
+
+static int set_err(int code, const char *msg) {
+    g_err = msg;
+    return code;
+}
+
+#define HIPCHK(expr)                                                                  \
+    do {                                                                              \
+        hipError_t _e = (expr);                                                       \
+        if (_e != hipSuccess) {                                                       \
+            g_err = std::string(#expr) + ": " + hipGetErrorString(_e);                \
+            return LSLAM_ERR_HIP;                                                     \
+        }                                                                             \
+    } while (0)
+
+// A grow-only device buffer of the context.  Growing frees the old allocation, which work in
+// flight may still use.  The rule: a grow first synchronises all four streams of the context,
+// whichever of them use the buffer (it happens only when a shape first grows).  A failed grow
+// leaves the buffer empty.
+struct DevBuf {
+    void *p = nullptr;
+    size_t bytes = 0;
+    template <typename T>
+    T *as() const { return (T *)p; }
+    hipError_t release() {
+        void *q = p;
+        p = nullptr;
+        bytes = 0;
+        return q ? hipFree(q) : hipSuccess;
+    }
+    static bool fits(const DevBuf *b, int n, size_t need) {
+        for (int i = 0; i < n; i++)
+            if (b[i].bytes < need) return false;
+        return true;
+    }
+    // b[0..n) grow as a group: all are freed before any is allocated
+    static int ensure(lslam_ctx *c, DevBuf *b, int n, size_t need, const char *what);
+    int ensure(lslam_ctx *c, size_t need, const char *what) { return ensure(c, this, 1, need, what); }
+};
+
+struct lslam_ctx {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool timing = false;
+    // per kernel id: a ring of (start, stop) event pairs harvested lazily, so
+    // timing never blocks the host between back-to-back launches
+    hipEvent_t ev0[LSLAM_K_COUNT][LSLAM_EV_RING] = {}, ev1[LSLAM_K_COUNT][LSLAM_EV_RING] = {};
+    int head[LSLAM_K_COUNT] = {}, npend[LSLAM_K_COUNT] = {};
+    double total_ms[LSLAM_K_COUNT] = {};
+    int64_t launches[LSLAM_K_COUNT] = {};
+    DevBuf scr;   // main-stream scratch: resolved draws (when the caller gives no draws_out)
+    DevBuf escr;  // express-scan revolution builder scratch (per-packet flags/ranks, per-revolution info)
+    DevBuf cscr;  // large-chunk consensus scratch: per-trial counts (+ Philox draws)
+    int resolve_beside = 0;  // this call's resolves will likely run beside the next call's producer
+    int n_cus = 1;           // compute units of the device
+    uint32_t timing_mask = 0xffffffffu;  // kernel ids timed when timing is on (lslam_set_timing_mask)
+    // reject tables of the table-mode parser, K = 2..127 (lslam_rng_pipe.h)
+    uint32_t *rt_all = nullptr;
+    // seed_kernel -> rng_kernel: initial MT states [n_scans][624].  [0], [1]: the pipeline's, by
+    // call parity, seeded on sstream ahead of their producers (seed_beside); [2]: producers on the
+    // ctx stream (lslam_hyp_mt19937), seeded in stream order
+    DevBuf seedst[3];
+    hipStream_t sstream = nullptr;
+    hipEvent_t ev_seeded[2] = {};     // on sstream, after seed_kernel into seedst[i]
+    hipEvent_t ev_seed_read[2] = {};  // on pstream, after the producer that read seedst[i]
+    int seed_next = 0;                // the pipeline's next seed buffer
+    // cut_lane_kernel -> chunk_kernel: [n_chunks] ChunkCut, a ring of four by seeded call: the
+    // buffer of call n is written after the producer of seeded call n - 2 (ev_seed_read), which
+    // waited for its slot, released by the fix-up of the mt call two before it -- after the
+    // consensus of seeded call n - 4, the buffer's previous reader
+    DevBuf cutb[4];
+    int cut_next = 0;
+    size_t steps_budget = default_steps_budget();  // producer slot budget (prepare_steps)
+    // The MT producer of call k+1 runs on its own stream while call k's
+    // consumers finish on `stream`: two producer slots (Fisher-Yates steps +
+    // end-of-scan MT state), each released by an event once its consumers ran.
+    // (Measured and dropped at r04: a third slot, 0.79-0.86 vs 0.76 ms per C3 step; the resolve
+    // on a stream of its own after its producer, 0.871 vs 0.763 ms.)
+    hipStream_t pstream = nullptr;
+    DevBuf pslot[NSLOTS];  // (one size: they grow together)
+    int next_slot = 0;
+    hipEvent_t ev_slot_free[NSLOTS] = {};  // on stream, after the slot's resolve + fix-up
+    hipEvent_t ev_produced = nullptr;      // on pstream, after rng_kernel
+    hipEvent_t ev_copy = nullptr;          // on stream, after the latest lslam_h2d / lslam_memset
+    hipEvent_t ev_call = nullptr;          // on stream, at the end of the latest pipeline call
+    // A UKF step that does not read the call's RANSAC results runs on its own
+    // stream beside the RANSAC chain; the main stream joins it before ev_call.
+    hipStream_t ustream = nullptr;
+    hipEvent_t ev_ukf = nullptr;  // on ustream, after the side UKF
+    // what the producer's waits are decided from (lslam_hazards.h); hz.prev_state_out is complete
+    // once ev_slot_free[prev_slot] fired
+    HazardState hz;
+    int prev_slot = 0;
+    DevBuf spec_dirty[2];  // [n_scans] replayed-by-fix-up flags, by call parity (they grow together)
+    int spec_cur = 0;      // the buffer the latest fix-up wrote
+};
+
+int DevBuf::ensure(lslam_ctx *c, DevBuf *b, int n, size_t need, const char *what) {
+    if (fits(b, n, need)) return LSLAM_OK;
+    for (hipStream_t s : {c->stream, c->pstream, c->ustream, c->sstream}) HIPCHK(hipStreamSynchronize(s));
+    for (int i = 0; i < n; i++) HIPCHK(b[i].release());
+    for (int i = 0; i < n; i++) {
+        const hipError_t e = hipMalloc(&b[i].p, need);
+        if (e == hipErrorOutOfMemory) {
+            g_err = std::string("hipMalloc: out of memory (") + what + ")";
+            return LSLAM_ERR_NOMEM;
+        }
+        HIPCHK(e);
+        b[i].bytes = need;
+    }
+    return LSLAM_OK;
+}
+
+// rows v = 0..127 of every K = 2..127, built once per process (rt_word, lslam_rng_pipe.h)
+static const std::vector<uint32_t> &reject_tables() {
+    static const std::vector<uint32_t> t = [] {
+        std::vector<uint32_t> v((size_t)(RT_KMAX - 1) * RT_DWORDS);
+        for (uint32_t K = 2; K <= RT_KMAX; K++)
+            for (uint32_t r = 0; r < (uint32_t)RT_ROWS; r++)
+                for (uint32_t q = 0; q < (uint32_t)RT_ST; q++)
+                    v[(size_t)(K - 2) * RT_DWORDS + r * RT_ST + q] = rt_word(K, r, q);
+        return v;
+    }();
+    return t;
+}
+
+// streams, events and the reject tables of a new context; on a failure lslam_ctx_create
+// destroys whatever exists by then
+static int ctx_init(lslam_ctx *c, int device) {
+    c->device = device;
+    HIPCHK(hipDeviceGetAttribute(&c->n_cus, hipDeviceAttributeMultiprocessorCount, device));
+    if (c->n_cus < 1) c->n_cus = 1;
+    if (const char *e = getenv("LSLAM_MT_SPECULATE")) c->hz.speculate = atoi(e) != 0;
+    HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+    for (int k = 0; k < LSLAM_K_COUNT; k++)
+        for (int r = 0; r < LSLAM_EV_RING; r++) {
+            HIPCHK(hipEventCreate(&c->ev0[k][r]));
+            HIPCHK(hipEventCreate(&c->ev1[k][r]));
+        }
+    // the producer's chains are the critical path: its stream gets the highest
+    // priority so that its workgroups are dispatched ahead of the previous call's
+    // consumers (resolve / consensus / post) that run beside it
+    {
+        int lo_pri = 0, hi_pri = 0;
+        if (hipDeviceGetStreamPriorityRange(&lo_pri, &hi_pri) != hipSuccess) hi_pri = 0;
+        HIPCHK(hipStreamCreateWithPriority(&c->pstream, hipStreamNonBlocking, hi_pri));
+    }
+    HIPCHK(hipStreamCreateWithFlags(&c->sstream, hipStreamNonBlocking));
+    for (int i = 0; i < 2; i++) {
+        HIPCHK(hipEventCreateWithFlags(&c->ev_seeded[i], hipEventDisableTiming));
+        HIPCHK(hipEventCreateWithFlags(&c->ev_seed_read[i], hipEventDisableTiming));
+        HIPCHK(hipEventRecord(c->ev_seed_read[i], c->stream));
+    }
+    for (int i = 0; i < NSLOTS; i++) HIPCHK(hipEventCreateWithFlags(&c->ev_slot_free[i], hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_produced, hipEventDisableTiming));
+    HIPCHK(hipStreamCreateWithFlags(&c->ustream, hipStreamNonBlocking));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_ukf, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_copy, hipEventDisableTiming));
+    HIPCHK(hipEventCreateWithFlags(&c->ev_call, hipEventDisableTiming));
+    for (int i = 0; i < NSLOTS; i++) HIPCHK(hipEventRecord(c->ev_slot_free[i], c->stream));
+    HIPCHK(hipEventRecord(c->ev_copy, c->stream));
+    HIPCHK(hipEventRecord(c->ev_call, c->stream));
+    const std::vector<uint32_t> &t = reject_tables();
+    HIPCHK(hipMalloc(&c->rt_all, t.size() * 4));
+    HIPCHK(hipMemcpy(c->rt_all, t.data(), t.size() * 4, hipMemcpyHostToDevice));
+    return LSLAM_OK;
+}
+
+extern "C" {
+
+#define LSLAM_STR_(x) #x
+#define LSLAM_STR(x) LSLAM_STR_(x)
+#ifndef LSLAM_SRC_HASH
+#define LSLAM_SRC_HASH "0000000000000000"  // lidar_slam_amd/build.py passes the sources' sha256 prefix
+#endif
+const char *lslam_version(void) {
+    return "lidarslam-mi355x 0.3.0 (abi " LSLAM_STR(LSLAM_ABI_VERSION) ", src " LSLAM_SRC_HASH ", gfx950)";
+}
+
+const char *lslam_status_string(int st) {
+    switch (st) {
+        case LSLAM_OK: return "ok";
+        case LSLAM_ERR_ARG: return "invalid argument";
+        case LSLAM_ERR_HIP: return "HIP runtime error";
+        case LSLAM_ERR_NOMEM: return "out of memory";
+        case LSLAM_ERR_CAPACITY: return "capacity exceeded";
+        case LSLAM_ERR_UNSUPPORTED: return "unsupported";
+        default: return "unknown status";
+    }
+}
+
+const char *lslam_last_error(void) { return g_err.c_str(); }
+
+int lslam_device_count(int *n) {
+    if (!n) return LSLAM_ERR_ARG;
+    int c = 0;
+    hipError_t e = hipGetDeviceCount(&c);
+    if (e != hipSuccess) c = 0;
+    *n = c;
+    return LSLAM_OK;
+}
+
+int lslam_ctx_create(int device, lslam_ctx **out) {
+    if (!out) return LSLAM_ERR_ARG;
+    *out = nullptr;
+    int n = 0;
+    HIPCHK(hipGetDeviceCount(&n));
+    if (device < 0 || device >= n) return set_err(LSLAM_ERR_ARG, "device index out of range");
+    HIPCHK(hipSetDevice(device));
+    lslam_ctx *c = new (std::nothrow) lslam_ctx();
+    if (!c) return LSLAM_ERR_NOMEM;
+    const int st = ctx_init(c, device);
+    if (st) {
+        lslam_ctx_destroy(c);  // (leaves g_err as ctx_init set it)
+        return st;
+    }
+    *out = c;
+    return LSLAM_OK;
+}
+
+// safe on a partially built context (lslam_ctx_create's failure path): every handle may be null
+int lslam_ctx_destroy(lslam_ctx *c) {
+    if (!c) return LSLAM_OK;
+    (void)hipSetDevice(c->device);
+    hipStream_t streams[4] = {c->stream, c->pstream, c->ustream, c->sstream};
+    for (hipStream_t s : streams)
+        if (s) (void)hipStreamSynchronize(s);
+    for (int k = 0; k < LSLAM_K_COUNT; k++)
+        for (int r = 0; r < LSLAM_EV_RING; r++) {
+            if (c->ev0[k][r]) (void)hipEventDestroy(c->ev0[k][r]);
+            if (c->ev1[k][r]) (void)hipEventDestroy(c->ev1[k][r]);
+        }
+    for (DevBuf *b : {&c->scr, &c->escr, &c->cscr}) (void)b->release();
+    for (DevBuf &b : c->seedst) (void)b.release();
+    for (DevBuf &b : c->cutb) (void)b.release();
+    for (DevBuf &b : c->pslot) (void)b.release();
+    for (DevBuf &b : c->spec_dirty) (void)b.release();
+    if (c->rt_all) (void)hipFree(c->rt_all);
+    hipEvent_t evs[10] = {c->ev_seeded[0], c->ev_seeded[1], c->ev_seed_read[0], c->ev_seed_read[1], c->ev_slot_free[0],
+                          c->ev_slot_free[1], c->ev_produced, c->ev_copy, c->ev_call, c->ev_ukf};
+    for (hipEvent_t e : evs)
+        if (e) (void)hipEventDestroy(e);
+    for (hipStream_t s : streams)
+        if (s) (void)hipStreamDestroy(s);
+    delete c;
+    return LSLAM_OK;
+}
+
+int lslam_sync(lslam_ctx *c) {
+    if (!c) return LSLAM_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipStreamSynchronize(c->pstream));
+    HIPCHK(hipStreamSynchronize(c->ustream));
+    HIPCHK(hipStreamSynchronize(c->sstream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return LSLAM_OK;
+}
+
+int lslam_malloc(lslam_ctx *c, size_t bytes, void **p) {
+    if (!c || !p) return LSLAM_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    *p = nullptr;
+    if (bytes == 0) bytes = 16;
+    hipError_t e = hipMalloc(p, bytes);
+    if (e == hipErrorOutOfMemory) return set_err(LSLAM_ERR_NOMEM, "hipMalloc: out of memory");
+    HIPCHK(e);
+    return LSLAM_OK;
+}
+
+int lslam_free(lslam_ctx *c, void *p) {
+    if (!c) return LSLAM_ERR_ARG;
+    if (!p) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    HIPCHK(hipFree(p));
+    return LSLAM_OK;
+}
+
+int lslam_host_alloc(size_t bytes, void **p) {
+    if (!p) return LSLAM_ERR_ARG;
+    HIPCHK(hipHostMalloc(p, bytes ? bytes : 16, hipHostMallocDefault));
+    return LSLAM_OK;
+}
+
+int lslam_host_free(void *p) {
+    if (p) HIPCHK(hipHostFree(p));
+    return LSLAM_OK;
+}
+
+int lslam_h2d(lslam_ctx *c, void *dst, const void *src, size_t n) {
+    if (!c || (!dst && n) || (!src && n)) return LSLAM_ERR_ARG;
+    if (!n) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // (the previous calls, which may still read dst, are ahead of this on the ctx stream)
+    HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->ev_copy, c->stream));
+    c->hz.copies.add(dst, n);
+    return LSLAM_OK;
+}
+
+int lslam_d2h(lslam_ctx *c, void *dst, const void *src, size_t n) {
+    if (!c || (!dst && n) || (!src && n)) return LSLAM_ERR_ARG;
+    if (!n) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // (the previous calls, which may still read dst, are ahead of this on the ctx stream)
+    HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToHost, c->stream));
+    return LSLAM_OK;
+}
+
+int lslam_d2d(lslam_ctx *c, void *dst, const void *src, size_t n) {
+    if (!c || (!dst && n) || (!src && n)) return LSLAM_ERR_ARG;
+    if (!n) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // (the previous calls, which may still read dst, are ahead of this on the ctx stream)
+    HIPCHK(hipMemcpyAsync(dst, src, n, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(hipEventRecord(c->ev_copy, c->stream));
+    c->hz.copies.add(dst, n);
+    return LSLAM_OK;
+}
+
+int lslam_host_register(void *p, size_t n) {
+    if (!p || !n) return LSLAM_ERR_ARG;
+    const hipError_t e = hipHostRegister(p, n, hipHostRegisterDefault);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();  // not sticky: the caller falls back to pageable copies
+        return set_err(LSLAM_ERR_HIP, hipGetErrorString(e));
+    }
+    return LSLAM_OK;
+}
+
+int lslam_host_unregister(void *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    HIPCHK(hipHostUnregister(p));
+    return LSLAM_OK;
+}
+
+int lslam_ctx_stream(lslam_ctx *c, void **stream) {
+    if (!c || !stream) return LSLAM_ERR_ARG;
+    *stream = (void *)c->stream;
+    return LSLAM_OK;
+}
+
+int lslam_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[7] = {(int64_t)sizeof(lslam_chunk_model), (int64_t)sizeof(lslam_landmark),
+                          (int64_t)sizeof(lslam_ransac_params), (int64_t)sizeof(lslam_ukf_params),
+                          (int64_t)sizeof(lslam_scan_batch), (int64_t)sizeof(lslam_express_measures),
+                          (int64_t)sizeof(lslam_express_revs)};
+    for (int i = 0; i < n && i < 7 && sizes; i++) sizes[i] = s[i];
+    return 7;
+}
+
+int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
+    if (!c || (!dst && n)) return LSLAM_ERR_ARG;
+    if (!n) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    // (the previous calls, which may still read dst, are ahead of this on the ctx stream)
+    HIPCHK(hipMemsetAsync(dst, v, n, c->stream));
+    HIPCHK(hipEventRecord(c->ev_copy, c->stream));
+    c->hz.copies.add(dst, n);
+    return LSLAM_OK;
+}
+
+// fold the oldest `keep_free` pending event pairs (all of them if < 0) into the totals
+static int harvest(lslam_ctx *c, int k, int upto_free = -1) {
+    while (c->npend[k] > 0 && (upto_free < 0 || LSLAM_EV_RING - c->npend[k] < upto_free)) {
+        const int r = (c->head[k] - c->npend[k] + LSLAM_EV_RING) % LSLAM_EV_RING;
+        HIPCHK(hipEventSynchronize(c->ev1[k][r]));
+        float ms = 0.f;
+        HIPCHK(hipEventElapsedTime(&ms, c->ev0[k][r], c->ev1[k][r]));
+        c->total_ms[k] += ms;
+        c->launches[k] += 1;
+        c->npend[k] -= 1;
+    }
+    return LSLAM_OK;
+}
+
+static int timer_begin(lslam_ctx *c, int k, hipStream_t st_ = nullptr) {
+    if (!c->timing || !((c->timing_mask >> k) & 1u)) return LSLAM_OK;
+    int st = harvest(c, k, 1);
+    if (st) return st;
+    HIPCHK(hipEventRecord(c->ev0[k][c->head[k]], st_ ? st_ : c->stream));
+    return LSLAM_OK;
+}
+
+static int timer_end(lslam_ctx *c, int k, hipStream_t st_ = nullptr) {
+    if (!c->timing || !((c->timing_mask >> k) & 1u)) return LSLAM_OK;
+    HIPCHK(hipEventRecord(c->ev1[k][c->head[k]], st_ ? st_ : c->stream));
+    c->head[k] = (c->head[k] + 1) % LSLAM_EV_RING;
+    c->npend[k] += 1;
+    return LSLAM_OK;
+}
+
+int lslam_set_timing(lslam_ctx *c, int en) {
+    if (!c) return LSLAM_ERR_ARG;
+    c->timing = en != 0;
+    return LSLAM_OK;
+}
+
+int lslam_set_timing_mask(lslam_ctx *c, uint32_t mask) {
+    if (!c) return LSLAM_ERR_ARG;
+    c->timing_mask = mask;
+    return LSLAM_OK;
+}
+
+int lslam_timing(lslam_ctx *c, int k, double *ms, int64_t *n) {
+    if (!c || k < 0 || k >= LSLAM_K_COUNT) return LSLAM_ERR_ARG;
+    HIPCHK(hipSetDevice(c->device));
+    int st = harvest(c, k);
+    if (st) return st;
+    if (ms) *ms = c->total_ms[k];
+    if (n) *n = c->launches[k];
+    return LSLAM_OK;
+}
+
+int lslam_timing_reset(lslam_ctx *c) {
+    if (!c) return LSLAM_ERR_ARG;
+    for (int k = 0; k < LSLAM_K_COUNT; k++) {
+        int st = harvest(c, k);
+        if (st) return st;
+        c->total_ms[k] = 0;
+        c->launches[k] = 0;
+    }
+    return LSLAM_OK;
+}
+
+int lslam_ransac_params_default(lslam_ransac_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->residual_threshold = 20.0;  // ransac_functions.py:9
+    p->max_trials = 100;           // :10
+    p->min_samples = 2;            // :11
+    p->hyp_source = LSLAM_HYP_MT19937;
+    p->life = 40;                  // landmarking.py:3
+    p->tol_a = 0.1;                // :4
+    p->tol_b = 10.0;               // :5
+    p->tol_dist = 100.0;           // :6
+    p->philox_seed = 0x5eed5eedull;
+    return LSLAM_OK;
+}
+
+int lslam_ukf_params_default(lslam_ukf_params *p, int32_t L) {
+    if (!p || L < 0) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->n_landmarks = L;
+    p->flags = LSLAM_UKF_PREDICT | LSLAM_UKF_UPDATE;
+    p->dt = 0.005;          // systemClass.py:10
+    p->wheel_radius = 50;   // UKFMethods.py:6
+    p->wheel_base = 200;    // UKFMethods.py:7
+    p->alpha = 1e-4;        // systemClass.py:20
+    p->beta = 2.0;
+    p->kappa = 0.0;
+    for (int i = 0; i < 9; i++) p->Q[i] = (i % 4 == 0) ? 0.001 : 0.0;  // systemClass.py:29
+    return LSLAM_OK;
+}
+
+double lslam_inlier_cutoff(double thr) {
+    if (isnan(thr)) return NAN;
+    if (!(thr > 0)) return 0.0;
+    if (isinf(thr)) return INFINITY;
+    double e = thr * thr;
+    while (e > 0 && sqrt(e) >= thr) e = nextafter(e, 0.0);
+    while (sqrt(e) < thr) e = nextafter(e, INFINITY);
+    return e;
+}
+
+int lslam_ukf_weights(const lslam_ukf_params *p, double *Wm, double *Wc, double *lpn) {
+    if (!p || !Wm || !Wc) return LSLAM_ERR_ARG;
+    // filterpy MerweScaledSigmaPoints._compute_weights, n = 3
+    const double n = 3.0;
+    const double lambda_ = p->alpha * p->alpha * (n + p->kappa) - n;
+    const double c = .5 / (n + lambda_);
+    for (int i = 0; i < 7; i++) Wm[i] = Wc[i] = c;
+    Wc[0] = lambda_ / (n + lambda_) + (1 - p->alpha * p->alpha + p->beta);
+    Wm[0] = lambda_ / (n + lambda_);
+    if (lpn) *lpn = lambda_ + n;
+    return LSLAM_OK;
+}
+
+int lslam_mt_seed_state(uint32_t seed, uint32_t *st) {
+    if (!st) return LSLAM_ERR_ARG;
+    for (int i = 0; i < 624; i++) {
+        st[i] = seed;
+        seed = 1812433253u * (seed ^ (seed >> 30)) + (uint32_t)(i + 1);
+    }
+    st[624] = 624;
+    return LSLAM_OK;
+}
+
+}  // extern "C"
+
