@@ -32,6 +32,8 @@
  *                         callbacks (filterpy 1.4.5 UnscentedKalmanFilter semantics)
  *   lslam_ukf_trace       the same, exposing UKFMethods.py:26-34 hx and :60-71
  *                         residuals for the reference-pinned tests
+ *   lslam_scan_match      nothing: the reference's robot.py holds a pose and no odometry; this is
+ *                         the wheel-speed input u of UKFMethods.py:17-24 made from the scans
  */
 #ifndef LIDARSLAM_H
 #define LIDARSLAM_H
@@ -43,7 +45,7 @@
 extern "C" {
 #endif
 
-#define LSLAM_ABI_VERSION 4
+#define LSLAM_ABI_VERSION 5
 
 /* ---- status codes ---- */
 enum {
@@ -230,6 +232,42 @@ typedef struct lslam_express_revs {
     int32_t cap_scans, cap_chunks;
 } lslam_express_revs;
 
+/* ---- scan-match flags (lslam_match_batch.flags) ---- */
+enum {
+    LSLAM_MATCH_EMPTY = 1,  /* no valid point on one side, or a winning score of 0: delta = 0, best = the centre */
+    LSLAM_MATCH_EDGE = 2    /* the winner lies on the window's border along some axis: the motion may exceed it */
+};
+
+/* Correlative scan matcher (lslam_scan_match).  Ranges: cell > 0, theta_step > 0, grid_w even in
+ * 16..512, smear 0..2, k_trans 0..15, k_theta 0..31. */
+typedef struct lslam_match_params {
+    double cell;        /* cell size, mm (20) */
+    double theta_step;  /* rotation step, rad (pi/360) */
+    int32_t grid_w;     /* cells per side of the look-up grid (512) */
+    int32_t smear;      /* smear radius, cells (2) */
+    int32_t k_trans;    /* translation half-window, cells (10): Nt = 2 k_trans + 1 */
+    int32_t k_theta;    /* rotation half-window, steps (20): Ntheta = 2 k_theta + 1 */
+} lslam_match_params;
+
+/* A batch of scan pairs, one per robot; all pointers DEVICE memory (NULL = absent where optional). */
+typedef struct lslam_match_batch {
+    int32_t n_scans;
+    int32_t reserved;
+    /* inputs */
+    const double *ref_xy;    /* [ref_off[n_scans]][2] previous revolutions, each in its own robot frame */
+    const int32_t *ref_off;  /* [n_scans+1] CSR robot -> reference points */
+    const double *cur_xy;    /* [cur_off[n_scans]][2] current revolutions */
+    const int32_t *cur_off;  /* [n_scans+1] */
+    const double *rot;       /* [Ntheta][2] (cos, sin) of (k - k_theta) * theta_step: the caller's bits */
+    /* outputs */
+    double *delta;           /* [n_scans][3] (tx mm, ty mm, dtheta rad): current frame in the previous one */
+    int32_t *best;           /* [n_scans][4] (k, jy, jx, score) of the winner */
+    int32_t *n_valid;        /* [n_scans][2] valid reference / current points */
+    int32_t *flags;          /* [n_scans] LSLAM_MATCH_* */
+    int32_t *scores;         /* [n_scans][Ntheta][Nt][Nt] the whole score volume (optional) */
+    double *ukf_u;           /* [n_scans][2] wheel speeds [vl, vr] (optional; written only with u != NULL) */
+} lslam_match_batch;
+
 typedef struct lslam_ctx lslam_ctx;  /* opaque: device, stream, events, scratch */
 
 /* ---- library / context ---- */
@@ -260,13 +298,15 @@ int lslam_host_unregister(void *hptr);
 int lslam_ctx_stream(lslam_ctx *ctx, void **stream);
 /* sizes (bytes) of the ABI structs as compiled into the library, in this order:
  * lslam_chunk_model, lslam_landmark, lslam_ransac_params, lslam_ukf_params, lslam_scan_batch,
- * lslam_express_measures, lslam_express_revs.  Writes min(n, 7) entries, returns 7. */
+ * lslam_express_measures, lslam_express_revs, lslam_match_params, lslam_match_batch.  Writes
+ * min(n, 9) entries, returns 9. */
 int lslam_abi_sizes(int64_t *sizes, int n);
 /* per-kernel HIP-event timing on the ctx stream (kernel ids: LSLAM_K_*) */
 enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMARK = 3, LSLAM_K_UKF = 4,
        LSLAM_K_RNG = 5 /* parity-stream producer */, LSLAM_K_CONSENSUS = 6 /* per-chunk A4-A8 */,
        LSLAM_K_EXPRESS = 7 /* a whole express decode / scans call */,
-       LSLAM_K_EXPRESS_SCATTER = 8 /* its decode + A1 + scatter kernel */, LSLAM_K_COUNT = 9 };
+       LSLAM_K_EXPRESS_SCATTER = 8 /* its decode + A1 + scatter kernel */,
+       LSLAM_K_MATCH = 9 /* a whole scan-match call */, LSLAM_K_COUNT = 10 };
 int lslam_set_timing(lslam_ctx *ctx, int enable);
 /* which kernel ids are timed while timing is on (bit k = LSLAM_K_k; default all).  Timing
  * events between the producer and consumer kernels change how the two streams overlap,
@@ -283,6 +323,7 @@ int lslam_set_steps_budget(lslam_ctx *ctx, int64_t bytes);
 /* ---- host helpers ---- */
 int lslam_ransac_params_default(lslam_ransac_params *p);
 int lslam_ukf_params_default(lslam_ukf_params *p, int32_t n_landmarks);
+int lslam_match_params_default(lslam_match_params *p);
 /* smallest e with RN(sqrt(e)) >= thr: (residual < thr) <=> (squared residual < cutoff) */
 double lslam_inlier_cutoff(double thr);
 /* MerweScaledSigmaPoints weights (filterpy _compute_weights) for n = 3 */
@@ -324,6 +365,31 @@ int lslam_ukf_trace(lslam_ctx *ctx, const lslam_scan_batch *b, const lslam_ukf_p
  * association / UKF post pass */
 int lslam_scan_pipeline(lslam_ctx *ctx, const lslam_scan_batch *b, const lslam_ransac_params *p,
                         const lslam_ukf_params *u);
+/* LiDAR-only odometry: a correlative scan match per robot, previous revolution (ref) against the
+ * current one (cur), giving the pose of the current frame in the previous one, q ~ R(theta) p + t.
+ * FP64, every operation rounded on its own; half = grid_w/2, inv = 1.0/cell, Nt = 2 k_trans + 1,
+ * Ntheta = 2 k_theta + 1.  A point is valid if both coordinates are finite and it is not exactly
+ * (0, 0) (the express decoder's invalid measure).
+ *   1. grid G [grid_w][grid_w]: a valid ref point with fx = floor(x inv), fy = floor(y inv), both
+ *      in [-half, half) (compared as doubles), occupies cell (fy + half, fx + half);
+ *      G[c] = max(0, smear + 1 - Chebyshev distance from c to the nearest occupied cell).
+ *   2. scores S[k][jy][jx] (int32): with (c, s) = rot[k], for each valid cur point
+ *      x' = c x - s y, y' = s x + c y, ax = floor(x' inv), ay = floor(y' inv);
+ *      S = sum of G[ay + (jy - k_trans) + half][ax + (jx - k_trans) + half], 0 outside the grid.
+ *   3. winner: the highest score, then the smallest d2 = (k - k_theta)^2 + (jy - k_trans)^2 +
+ *      (jx - k_trans)^2, then the smallest flat index (k Nt + jy) Nt + jx.
+ *   4. per axis, with the winner's neighbours s-, s+ and its score s0: den = s- - 2 s0 + s+; off
+ *      the window's border and with den < 0 the offset is 0.5 (s- - s+) / den, else 0.
+ *   5. delta = ((jx - k_trans + ox) cell, (jy - k_trans + oy) cell, (k - k_theta + ot) theta_step),
+ *      best = (k, jy, jx, score); LSLAM_MATCH_EDGE if the winner is on the border along some axis;
+ *      a winning score of 0 gives LSLAM_MATCH_EMPTY alone, delta = 0, best = the centre.
+ *   6. with u != NULL and ukf_u given, the wheel speeds that UKFMethods.py:17-24 (x += dt B(theta) u)
+ *      turns back into (tx, dtheta): a = tx / (wheel_radius dt), b = dtheta wheel_base /
+ *      (2 wheel_radius dt), ukf_u = (a - b, a + b); (0, 0) when EMPTY.  ty stays in delta only.
+ * Runs on the context's main stream, after every earlier call.  Out-of-range parameters and
+ * missing required pointers return LSLAM_ERR_ARG; n_scans == 0 does nothing. */
+int lslam_scan_match(lslam_ctx *ctx, const lslam_match_batch *b, const lslam_match_params *p,
+                     const lslam_ukf_params *u);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LSLAM_LIB") or os.path.join(_HERE, "liblidarslam.so")  # override: experiments
 
 # ---- constants mirrored from include/lidarslam.h ----
-ABI_VERSION = 4  # include/lidarslam.h LSLAM_ABI_VERSION (struct layouts below)
+ABI_VERSION = 5  # include/lidarslam.h LSLAM_ABI_VERSION (struct layouts below)
 LSLAM_OK = 0
 LSLAM_ERR_ARG = -1
 LSLAM_ERR_HIP = -2
@@ -29,7 +29,8 @@ CAPACITY, CHUNK_BOUND = 256, 512
 HYP_MT19937, HYP_PHILOX, HYP_EXPLICIT = 0, 1, 2
 UKF_PREDICT, UKF_UPDATE, UKF_LMK_FROM_RANSAC, UKF_MAP, UKF_SIGMAS_IN = 1, 2, 4, 8, 16
 K_POLAR, K_HYP, K_PIPELINE, K_LANDMARK, K_UKF, K_RNG, K_CONSENSUS = 0, 1, 2, 3, 4, 5, 6
-K_EXPRESS, K_EXPRESS_SCATTER = 7, 8
+K_EXPRESS, K_EXPRESS_SCATTER, K_MATCH = 7, 8, 9
+MATCH_EMPTY, MATCH_EDGE = 1, 2
 
 
 class HIPLibraryError(RuntimeError):
@@ -82,6 +83,17 @@ class ExpressRevs(C.Structure):
                [("cap_points", C.c_int64), ("cap_scans", C.c_int32), ("cap_chunks", C.c_int32)]
 
 
+class MatchParams(C.Structure):
+    _fields_ = [("cell", C.c_double), ("theta_step", C.c_double), ("grid_w", C.c_int32), ("smear", C.c_int32),
+                ("k_trans", C.c_int32), ("k_theta", C.c_int32)]
+
+
+class MatchBatch(C.Structure):
+    _fields_ = [("n_scans", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, _VP) for n in ("ref_xy", "ref_off", "cur_xy", "cur_off", "rot", "delta", "best", "n_valid",
+                                   "flags", "scores", "ukf_u")]
+
+
 assert C.sizeof(ChunkModel) == 112
 assert C.sizeof(LandmarkRec) == 56
 
@@ -94,6 +106,7 @@ EXPORTS = [
     "lslam_ransac_params_default", "lslam_ukf_params_default", "lslam_inlier_cutoff", "lslam_ukf_weights",
     "lslam_mt_seed_state", "lslam_polar_to_xy", "lslam_hyp_mt19937", "lslam_ransac", "lslam_landmarks",
     "lslam_ukf_step", "lslam_ukf_trace", "lslam_scan_pipeline", "lslam_express_decode", "lslam_express_scans",
+    "lslam_match_params_default", "lslam_scan_match",
 ]
 
 _lib = None
@@ -157,6 +170,8 @@ def load():
         "lslam_scan_pipeline": ([_VP, P(ScanBatch), P(RansacParams), P(UkfParams)], C.c_int),
         "lslam_express_decode": ([_VP, _VP, i64, P(ExpressMeasures)], C.c_int),
         "lslam_express_scans": ([_VP, _VP, i64, i32, P(ExpressRevs)], C.c_int),
+        "lslam_match_params_default": ([P(MatchParams)], C.c_int),
+        "lslam_scan_match": ([_VP, P(MatchBatch), P(MatchParams), P(UkfParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -183,10 +198,10 @@ def _check_abi(L):
                                % (LIB_PATH, ver, ABI_VERSION))
         raise _err
     _check_source(m.group(2))
-    got = (C.c_int64 * 7)()
-    L.lslam_abi_sizes(got, 7)
+    got = (C.c_int64 * 9)()
+    L.lslam_abi_sizes(got, 9)
     want = [C.sizeof(t) for t in (ChunkModel, LandmarkRec, RansacParams, UkfParams, ScanBatch, ExpressMeasures,
-                                  ExpressRevs)]
+                                  ExpressRevs, MatchParams, MatchBatch)]
     if list(got) != want:
         _err = HIPLibraryError("struct sizes differ between %s %s and the ctypes layouts %s"
                                % (LIB_PATH, list(got), want))
@@ -237,4 +252,12 @@ def ukf_params(n_landmarks, **kw):
                 p.Q[i] = float(q)
         else:
             setattr(p, k, v)
+    return p
+
+
+def match_params(**kw):
+    p = MatchParams()
+    load().lslam_match_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
     return p

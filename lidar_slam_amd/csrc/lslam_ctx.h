@@ -63,6 +63,7 @@ struct lslam_ctx {
     DevBuf scr;   // main-stream scratch: resolved draws (when the caller gives no draws_out)
     DevBuf escr;  // express-scan revolution builder scratch (per-packet flags/ranks, per-revolution info)
     DevBuf cscr;  // large-chunk consensus scratch: per-trial counts (+ Philox draws)
+    DevBuf mscr;  // scan-match score volume (when the caller gives no scores)
     int resolve_beside = 0;  // this call's resolves will likely run beside the next call's producer
     int n_cus = 1;           // compute units of the device
     uint32_t timing_mask = 0xffffffffu;  // kernel ids timed when timing is on (lslam_set_timing_mask)
@@ -242,7 +243,7 @@ int lslam_ctx_destroy(lslam_ctx *c) {
             if (c->ev0[k][r]) (void)hipEventDestroy(c->ev0[k][r]);
             if (c->ev1[k][r]) (void)hipEventDestroy(c->ev1[k][r]);
         }
-    for (DevBuf *b : {&c->scr, &c->escr, &c->cscr}) (void)b->release();
+    for (DevBuf *b : {&c->scr, &c->escr, &c->cscr, &c->mscr}) (void)b->release();
     for (DevBuf &b : c->seedst) (void)b.release();
     for (DevBuf &b : c->cutb) (void)b.release();
     for (DevBuf &b : c->pslot) (void)b.release();
@@ -352,12 +353,13 @@ int lslam_ctx_stream(lslam_ctx *c, void **stream) {
 }
 
 int lslam_abi_sizes(int64_t *sizes, int n) {
-    const int64_t s[7] = {(int64_t)sizeof(lslam_chunk_model), (int64_t)sizeof(lslam_landmark),
+    const int64_t s[9] = {(int64_t)sizeof(lslam_chunk_model), (int64_t)sizeof(lslam_landmark),
                           (int64_t)sizeof(lslam_ransac_params), (int64_t)sizeof(lslam_ukf_params),
                           (int64_t)sizeof(lslam_scan_batch), (int64_t)sizeof(lslam_express_measures),
-                          (int64_t)sizeof(lslam_express_revs)};
-    for (int i = 0; i < n && i < 7 && sizes; i++) sizes[i] = s[i];
-    return 7;
+                          (int64_t)sizeof(lslam_express_revs), (int64_t)sizeof(lslam_match_params),
+                          (int64_t)sizeof(lslam_match_batch)};
+    for (int i = 0; i < n && i < 9 && sizes; i++) sizes[i] = s[i];
+    return 9;
 }
 
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
@@ -461,6 +463,18 @@ int lslam_ukf_params_default(lslam_ukf_params *p, int32_t L) {
     p->beta = 2.0;
     p->kappa = 0.0;
     for (int i = 0; i < 9; i++) p->Q[i] = (i % 4 == 0) ? 0.001 : 0.0;  // systemClass.py:29
+    return LSLAM_OK;
+}
+
+int lslam_match_params_default(lslam_match_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->cell = 20.0;                  // mm: a 512-cell grid spans +-5.12 m
+    p->theta_step = LS_PI / 360.0;   // half a degree
+    p->grid_w = 512;
+    p->smear = 2;
+    p->k_trans = 10;                 // +-200 mm
+    p->k_theta = 20;                 // +-10 degrees
     return LSLAM_OK;
 }
 

@@ -751,6 +751,82 @@ static int run_split(lslam_ctx *c, const lslam_scan_batch *b, const lslam_ransac
 }
 
 
+// ---- scan matcher (lslam_match.h) ----
+
+static int match_check_params(const lslam_match_params *p) {
+    if (!p) return set_err(LSLAM_ERR_ARG, "match: params is NULL");
+    if (!(p->cell > 0) || !std::isfinite(p->cell)) return set_err(LSLAM_ERR_ARG, "match: cell must be > 0");
+    if (!(p->theta_step > 0) || !std::isfinite(p->theta_step))
+        return set_err(LSLAM_ERR_ARG, "match: theta_step must be > 0");
+    if (p->grid_w < 16 || p->grid_w > 512 || (p->grid_w & 1))
+        return set_err(LSLAM_ERR_ARG, "match: grid_w must be even, in [16, 512]");
+    if (p->smear < 0 || p->smear > 2) return set_err(LSLAM_ERR_ARG, "match: smear must be in [0, 2]");
+    if (p->k_trans < 0 || p->k_trans > 15) return set_err(LSLAM_ERR_ARG, "match: k_trans must be in [0, 15]");
+    if (p->k_theta < 0 || p->k_theta > 31) return set_err(LSLAM_ERR_ARG, "match: k_theta must be in [0, 31]");
+    return LSLAM_OK;
+}
+
+// match_search_kernel on a grid of (robots x rotation slices), then match_pick_kernel per robot.
+// Slices: enough for two workgroups per CU (what the LDS allows) when the robots alone do not
+// give them, at most one per rotation; each slice rebuilds G.
+static int launch_match(lslam_ctx *c, const lslam_match_batch *b, const lslam_match_params *p,
+                        const lslam_ukf_params *u) {
+    MatchArgs k;
+    memset(&k, 0, sizeof(k));
+    k.b = *b;
+    k.cell = p->cell;
+    k.inv = 1.0 / p->cell;
+    k.theta_step = p->theta_step;
+    k.grid_w = p->grid_w;
+    k.half = p->grid_w / 2;
+    k.smear = p->smear;
+    k.kt = p->k_trans;
+    k.kth = p->k_theta;
+    k.Nt = 2 * p->k_trans + 1;
+    k.Nth = 2 * p->k_theta + 1;
+    k.W = p->grid_w + 2 * p->k_trans;
+    k.Sd = match_row_dwords(k.W);
+    k.write_u = (u && b->ukf_u) ? 1 : 0;
+    if (k.write_u) {
+        k.dt = u->dt;
+        k.wr = u->wheel_radius;
+        k.wb = u->wheel_base;
+    }
+    const int64_t want = 2 * (int64_t)c->n_cus;
+    int64_t ns = (want + b->n_scans - 1) / b->n_scans;
+    ns = std::min<int64_t>(std::max<int64_t>(ns, 1), k.Nth);
+    k.per_slice = (int)((k.Nth + ns - 1) / ns);
+    k.n_slices = (k.Nth + k.per_slice - 1) / k.per_slice;
+    if ((int64_t)b->n_scans * k.n_slices >= ((int64_t)1 << 31))
+        return set_err(LSLAM_ERR_UNSUPPORTED, "match: too many robots in one call");
+    const size_t vol = (size_t)b->n_scans * k.Nth * k.Nt * k.Nt * 4;
+    if (b->scores) {
+        k.scores = b->scores;
+    } else {
+        int st = c->mscr.ensure(c, vol, "match scores");
+        if (st) return st;
+        k.scores = c->mscr.as<int32_t>();
+    }
+    const int lds = match_lds_bytes(k.W, k.Sd, k.Nt);
+    static std::once_flag once;
+    std::call_once(once, [] { set_max_lds(match_search_kernel); });
+    int st = timer_begin(c, LSLAM_K_MATCH);
+    if (st) return st;
+    hipLaunchKernelGGL(match_search_kernel, dim3((unsigned)(b->n_scans * k.n_slices)), dim3(MATCH_TPB), lds, c->stream, k);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(match_pick_kernel, dim3((unsigned)b->n_scans), dim3(MATCH_PICK_TPB), 0, c->stream, k);
+    HIPCHK(hipGetLastError());
+    if ((st = timer_end(c, LSLAM_K_MATCH))) return st;
+    const size_t S = (size_t)b->n_scans;
+    c->hz.outs.add(b->delta, S * 24);
+    c->hz.outs.add(b->best, S * 16);
+    c->hz.outs.add(b->n_valid, S * 8);
+    c->hz.outs.add(b->flags, S * 4);
+    c->hz.outs.add(b->scores, vol);
+    if (k.write_u) c->hz.outs.add(b->ukf_u, S * 16);
+    return LSLAM_OK;
+}
+
 // ---- express-scan codec (lslam_express.h) ----
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -903,6 +979,27 @@ int lslam_scan_pipeline(lslam_ctx *c, const lslam_scan_batch *b, const lslam_ran
     if (u && ((u->flags & LSLAM_UKF_SIGMAS_IN) || b->ukf_sigmas))
         return set_err(LSLAM_ERR_UNSUPPORTED, "ukf_sigmas / LSLAM_UKF_SIGMAS_IN are lslam_ukf_step's (filterpy's cache)");
     return run_split(c, b, p, u);
+}
+
+// (the checks that need no device come first, the context last: tests/test_scanmatch_ref.py)
+int lslam_scan_match(lslam_ctx *c, const lslam_match_batch *b, const lslam_match_params *p,
+                     const lslam_ukf_params *u) {
+    int st = match_check_params(p);
+    if (st) return st;
+    if (!b) return set_err(LSLAM_ERR_ARG, "match: batch is NULL");
+    if (b->n_scans < 0) return set_err(LSLAM_ERR_ARG, "match: negative n_scans");
+    if (b->n_scans > 0) {
+        if (!b->ref_xy || !b->ref_off || !b->cur_xy || !b->cur_off || !b->rot)
+            return set_err(LSLAM_ERR_ARG, "match: missing input (ref_xy, ref_off, cur_xy, cur_off, rot)");
+        if (!b->delta || !b->best || !b->n_valid || !b->flags)
+            return set_err(LSLAM_ERR_ARG, "match: missing output (delta, best, n_valid, flags)");
+        if (u && b->ukf_u && (!(u->dt > 0) || !(u->wheel_radius > 0)))
+            return set_err(LSLAM_ERR_ARG, "match: wheel speeds need dt > 0 and wheel_radius > 0");
+    }
+    if (!c) return set_err(LSLAM_ERR_ARG, "match: ctx is NULL");
+    if (b->n_scans == 0) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return launch_match(c, b, p, u);
 }
 
 int lslam_express_decode(lslam_ctx *c, const uint8_t *packets, int64_t n_packets, const lslam_express_measures *out) {
