@@ -34,6 +34,8 @@
  *                         residuals for the reference-pinned tests
  *   lslam_scan_match      nothing: the reference's robot.py holds a pose and no odometry; this is
  *                         the wheel-speed input u of UKFMethods.py:17-24 made from the scans
+ *   lslam_grid_update     nothing persistent: mainWindow.py draws the last revolution's points
+ *                         (allSeries.replace) and forgets them; this keeps a log-odds map of them
  */
 #ifndef LIDARSLAM_H
 #define LIDARSLAM_H
@@ -45,7 +47,7 @@
 extern "C" {
 #endif
 
-#define LSLAM_ABI_VERSION 5
+#define LSLAM_ABI_VERSION 6
 
 /* ---- status codes ---- */
 enum {
@@ -268,6 +270,43 @@ typedef struct lslam_match_batch {
     double *ukf_u;           /* [n_scans][2] wheel speeds [vl, vr] (optional; written only with u != NULL) */
 } lslam_match_batch;
 
+/* ---- occupancy-grid flags (lslam_grid_batch.flags) ---- */
+enum {
+    LSLAM_GRID_BAD_POSE = 1,  /* a non-finite pose or origin, or a robot cell 2^20 or more cells off: grid untouched */
+    LSLAM_GRID_CLIPPED = 2    /* some cell of some ray lies outside the grid */
+};
+
+/* Occupancy-grid mapping (lslam_grid_update), 40 bytes.  Ranges: cell > 0; max_range > 0, finite,
+ * max_range / cell <= 4096; grid_w 16..2048; l_hit 1..1024; l_miss -1024..-1;
+ * -32768 <= l_min < 0 < l_max <= 32767. */
+typedef struct lslam_grid_params {
+    double cell;       /* cell size, mm (20) */
+    double max_range;  /* returns farther than this are ignored, mm (8000) */
+    int32_t grid_w;    /* cells per side (512) */
+    int32_t l_hit;     /* log-odds of a hit, 0.01 nat (85: p = 0.7) */
+    int32_t l_miss;    /* log-odds of a pass, 0.01 nat (-41: p = 0.4) */
+    int32_t l_min;     /* clamp (-200: p ~ 0.12) */
+    int32_t l_max;     /* clamp (350: p ~ 0.97) */
+    int32_t reserved;
+} lslam_grid_params;
+
+/* One revolution per robot, 72 bytes; all pointers DEVICE memory, all required. */
+typedef struct lslam_grid_batch {
+    int32_t n_robots;
+    int32_t reserved;
+    /* inputs */
+    const double *xy;       /* [pt_off[n_robots]][2] revolutions, each in its robot's frame */
+    const int32_t *pt_off;  /* [n_robots+1] CSR robot -> points */
+    const double *pose;     /* [n_robots][3] (x mm, y mm, theta rad), e.g. the filter's ukf_x */
+    const double *origin;   /* [n_robots][2] world coordinates of the corner of cell (0, 0) */
+    /* in/out */
+    int16_t *logodds;       /* [n_robots][grid_w][grid_w], row Y, units of 0.01 nat */
+    /* outputs */
+    double *rot;            /* [n_robots][2] (cos theta, sin theta) as used */
+    int32_t *n_used;        /* [n_robots][2] points traced / valid points beyond max_range */
+    int32_t *flags;         /* [n_robots] LSLAM_GRID_* */
+} lslam_grid_batch;
+
 typedef struct lslam_ctx lslam_ctx;  /* opaque: device, stream, events, scratch */
 
 /* ---- library / context ---- */
@@ -301,12 +340,16 @@ int lslam_ctx_stream(lslam_ctx *ctx, void **stream);
  * lslam_express_measures, lslam_express_revs, lslam_match_params, lslam_match_batch.  Writes
  * min(n, 9) entries, returns 9. */
 int lslam_abi_sizes(int64_t *sizes, int n);
+/* the same for the structs added since: lslam_grid_params, lslam_grid_batch.  Writes min(n, 2)
+ * entries, returns 2. */
+int lslam_grid_abi_sizes(int64_t *sizes, int n);
 /* per-kernel HIP-event timing on the ctx stream (kernel ids: LSLAM_K_*) */
 enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMARK = 3, LSLAM_K_UKF = 4,
        LSLAM_K_RNG = 5 /* parity-stream producer */, LSLAM_K_CONSENSUS = 6 /* per-chunk A4-A8 */,
        LSLAM_K_EXPRESS = 7 /* a whole express decode / scans call */,
        LSLAM_K_EXPRESS_SCATTER = 8 /* its decode + A1 + scatter kernel */,
-       LSLAM_K_MATCH = 9 /* a whole scan-match call */, LSLAM_K_COUNT = 10 };
+       LSLAM_K_MATCH = 9 /* a whole scan-match call */, LSLAM_K_GRID = 10 /* a whole grid update */,
+       LSLAM_K_COUNT = 11 };
 int lslam_set_timing(lslam_ctx *ctx, int enable);
 /* which kernel ids are timed while timing is on (bit k = LSLAM_K_k; default all).  Timing
  * events between the producer and consumer kernels change how the two streams overlap,
@@ -324,6 +367,7 @@ int lslam_set_steps_budget(lslam_ctx *ctx, int64_t bytes);
 int lslam_ransac_params_default(lslam_ransac_params *p);
 int lslam_ukf_params_default(lslam_ukf_params *p, int32_t n_landmarks);
 int lslam_match_params_default(lslam_match_params *p);
+int lslam_grid_params_default(lslam_grid_params *p);
 /* smallest e with RN(sqrt(e)) >= thr: (residual < thr) <=> (squared residual < cutoff) */
 double lslam_inlier_cutoff(double thr);
 /* MerweScaledSigmaPoints weights (filterpy _compute_weights) for n = 3 */
@@ -390,6 +434,37 @@ int lslam_scan_pipeline(lslam_ctx *ctx, const lslam_scan_batch *b, const lslam_r
  * missing required pointers return LSLAM_ERR_ARG; n_scans == 0 does nothing. */
 int lslam_scan_match(lslam_ctx *ctx, const lslam_match_batch *b, const lslam_match_params *p,
                      const lslam_ukf_params *u);
+/* Occupancy-grid mapping: one revolution per robot and the robot's pose -> the robot's grid of
+ * clamped log-odds (the inverse sensor model: the cells a beam crosses are free, the cell it ends
+ * in is occupied).  Per robot r, in FP64 with every operation rounded on its own, inv = 1.0 / cell:
+ *   0. pose and rotation: (px, py, theta) = pose[r], (ox, oy) = origin[r], the world coordinates of
+ *      the corner of cell (0, 0).  The library computes (c, s) = (cos theta, sin theta) and writes
+ *      them to rot[r] (always, NaN for a non-finite theta); the written bits are the definition's
+ *      input from here on.  Robot cell, as doubles: X0 = floor((px - ox) inv),
+ *      Y0 = floor((py - oy) inv).  If any of the five inputs is not finite, or |X0| or |Y0| >= 2^20:
+ *      flags[r] = LSLAM_GRID_BAD_POSE, n_used[r] = (0, 0) and the robot's grid is not touched.
+ *   1. points: valid as in lslam_scan_match (both coordinates finite, not exactly (0, 0)).  A valid
+ *      point with x x + y y > max_range max_range is counted in n_used[r][1] and ignored.  The
+ *      others are counted in n_used[r][0]; for them wx = px + (c x - s y), wy = py + (s x + c y),
+ *      X1 = floor((wx - ox) inv), Y1 = floor((wy - oy) inv).
+ *   2. ray, in integers: dx = X1 - X0, dy = Y1 - Y0, n = max(|dx|, |dy|).  The free cells are
+ *      i = 0 .. n-1: (X0 + sgn(dx) ((2 i |dx| + n) div 2n), Y0 + sgn(dy) ((2 i |dy| + n) div 2n));
+ *      the hit cell is (X1, Y1); with n = 0 there is only the hit.  The form is closed on purpose:
+ *      every cell of a ray is independent of the others, so lanes can share a ray and a tile can
+ *      clip a ray to an i-interval.  max_range / cell <= 4096 keeps 2 i |d| + n far inside int32.
+ *   3. per-revolution sum: D[Y][X] = l_hit (rays that hit the cell) + l_miss (rays that pass it
+ *      free), over the cells inside [0, grid_w)^2; cells outside are ignored.  LSLAM_GRID_CLIPPED is
+ *      set iff some cell of some ray lies outside: n_used[r][0] > 0 and the robot cell is outside,
+ *      or some hit cell is outside (a ray's cells lie in the bounding box of its two ends).
+ *   4. update, once per call: where D != 0, L' = clamp(L + D, l_min, l_max); every other cell keeps
+ *      its value, including a value outside the clamp range that the caller put there.  L is
+ *      int16 [n_robots][grid_w][grid_w], row Y, in units of 0.01 nat.  The sum is taken before the
+ *      single clamp, so the result does not depend on the order of rays or atomics.
+ * Runs on the context's main stream, after every earlier call: it sees the ukf_x that a preceding
+ * lslam_scan_pipeline or lslam_ukf_step wrote, and reads xy in place.  Out-of-range parameters and
+ * missing pointers return LSLAM_ERR_ARG (the message names the field), checked before the context
+ * is touched; n_robots == 0 does nothing. */
+int lslam_grid_update(lslam_ctx *ctx, const lslam_grid_batch *b, const lslam_grid_params *p);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LSLAM_LIB") or os.path.join(_HERE, "liblidarslam.so")  # override: experiments
 
 # ---- constants mirrored from include/lidarslam.h ----
-ABI_VERSION = 5  # include/lidarslam.h LSLAM_ABI_VERSION (struct layouts below)
+ABI_VERSION = 6  # include/lidarslam.h LSLAM_ABI_VERSION (struct layouts below)
 LSLAM_OK = 0
 LSLAM_ERR_ARG = -1
 LSLAM_ERR_HIP = -2
@@ -29,8 +29,9 @@ CAPACITY, CHUNK_BOUND = 256, 512
 HYP_MT19937, HYP_PHILOX, HYP_EXPLICIT = 0, 1, 2
 UKF_PREDICT, UKF_UPDATE, UKF_LMK_FROM_RANSAC, UKF_MAP, UKF_SIGMAS_IN = 1, 2, 4, 8, 16
 K_POLAR, K_HYP, K_PIPELINE, K_LANDMARK, K_UKF, K_RNG, K_CONSENSUS = 0, 1, 2, 3, 4, 5, 6
-K_EXPRESS, K_EXPRESS_SCATTER, K_MATCH = 7, 8, 9
+K_EXPRESS, K_EXPRESS_SCATTER, K_MATCH, K_GRID = 7, 8, 9, 10
 MATCH_EMPTY, MATCH_EDGE = 1, 2
+GRID_BAD_POSE, GRID_CLIPPED = 1, 2
 
 
 class HIPLibraryError(RuntimeError):
@@ -94,6 +95,16 @@ class MatchBatch(C.Structure):
                                    "flags", "scores", "ukf_u")]
 
 
+class GridParams(C.Structure):
+    _fields_ = [("cell", C.c_double), ("max_range", C.c_double)] + \
+               [(n, C.c_int32) for n in ("grid_w", "l_hit", "l_miss", "l_min", "l_max", "reserved")]
+
+
+class GridBatch(C.Structure):
+    _fields_ = [("n_robots", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, _VP) for n in ("xy", "pt_off", "pose", "origin", "logodds", "rot", "n_used", "flags")]
+
+
 assert C.sizeof(ChunkModel) == 112
 assert C.sizeof(LandmarkRec) == 56
 
@@ -107,6 +118,7 @@ EXPORTS = [
     "lslam_mt_seed_state", "lslam_polar_to_xy", "lslam_hyp_mt19937", "lslam_ransac", "lslam_landmarks",
     "lslam_ukf_step", "lslam_ukf_trace", "lslam_scan_pipeline", "lslam_express_decode", "lslam_express_scans",
     "lslam_match_params_default", "lslam_scan_match",
+    "lslam_grid_abi_sizes", "lslam_grid_params_default", "lslam_grid_update",
 ]
 
 _lib = None
@@ -172,6 +184,9 @@ def load():
         "lslam_express_scans": ([_VP, _VP, i64, i32, P(ExpressRevs)], C.c_int),
         "lslam_match_params_default": ([P(MatchParams)], C.c_int),
         "lslam_scan_match": ([_VP, P(MatchBatch), P(MatchParams), P(UkfParams)], C.c_int),
+        "lslam_grid_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_grid_params_default": ([P(GridParams)], C.c_int),
+        "lslam_grid_update": ([_VP, P(GridBatch), P(GridParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -202,6 +217,9 @@ def _check_abi(L):
     L.lslam_abi_sizes(got, 9)
     want = [C.sizeof(t) for t in (ChunkModel, LandmarkRec, RansacParams, UkfParams, ScanBatch, ExpressMeasures,
                                   ExpressRevs, MatchParams, MatchBatch)]
+    got2 = (C.c_int64 * 2)()
+    L.lslam_grid_abi_sizes(got2, 2)
+    got, want = list(got) + list(got2), want + [C.sizeof(GridParams), C.sizeof(GridBatch)]
     if list(got) != want:
         _err = HIPLibraryError("struct sizes differ between %s %s and the ctypes layouts %s"
                                % (LIB_PATH, list(got), want))
@@ -258,6 +276,14 @@ def ukf_params(n_landmarks, **kw):
 def match_params(**kw):
     p = MatchParams()
     load().lslam_match_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def grid_params(**kw):
+    p = GridParams()
+    load().lslam_grid_params_default(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

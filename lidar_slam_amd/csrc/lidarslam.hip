@@ -5,7 +5,8 @@
 // One translation unit.  This file holds the kernels; their device code is in
 //   lslam_wave.h (wave primitives), lslam_rng.h / lslam_rng_pipe.h (MT19937, Philox, the
 //   stream parser), lslam_ransac.h (fits, residuals), lslam_ukf.h, lslam_express.h (the
-//   express-packet kernels), lslam_match.h (the scan matcher's two kernels);
+//   express-packet kernels), lslam_match.h (the scan matcher's two kernels), lslam_grid.h
+//   (the occupancy-grid kernel; its integer ray is lslam_grid_ray.h, plain C++);
 // the host side is included at the foot:
 //   lslam_hazards.h  which waits a call's producer needs (plain C++, no HIP)
 //   lslam_ctx.h      lslam_ctx, its grow-only device buffers and timers, create / destroy,
@@ -3043,6 +3044,8 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
 
 // the scan matcher's kernels: after every other kernel, whose places in the code object they leave alone
 #include "lslam_match.h"
+// the occupancy-grid kernel, after those
+#include "lslam_grid.h"
 
 // ------------------------------------------------------------------------
 // host side: the context, then the launchers and entry points

@@ -362,6 +362,12 @@ int lslam_abi_sizes(int64_t *sizes, int n) {
     return 9;
 }
 
+int lslam_grid_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[2] = {(int64_t)sizeof(lslam_grid_params), (int64_t)sizeof(lslam_grid_batch)};
+    for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
+    return 2;
+}
+
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
     if (!c || (!dst && n)) return LSLAM_ERR_ARG;
     if (!n) return LSLAM_OK;
@@ -475,6 +481,19 @@ int lslam_match_params_default(lslam_match_params *p) {
     p->smear = 2;
     p->k_trans = 10;                 // +-200 mm
     p->k_theta = 20;                 // +-10 degrees
+    return LSLAM_OK;
+}
+
+int lslam_grid_params_default(lslam_grid_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->cell = 20.0;         // mm: a 512-cell grid spans 10.24 m
+    p->max_range = 8000.0;  // mm
+    p->grid_w = 512;
+    p->l_hit = 85;          // ln(0.7 / 0.3), 0.01 nat
+    p->l_miss = -41;        // ln(0.4 / 0.6)
+    p->l_min = -200;        // p ~ 0.12
+    p->l_max = 350;         // p ~ 0.97
     return LSLAM_OK;
 }
 

@@ -827,6 +827,68 @@ static int launch_match(lslam_ctx *c, const lslam_match_batch *b, const lslam_ma
     return LSLAM_OK;
 }
 
+// ---- occupancy grid (lslam_grid.h) ----
+
+static int grid_check_params(const lslam_grid_params *p) {
+    if (!p) return set_err(LSLAM_ERR_ARG, "grid: params is NULL");
+    if (!(p->cell > 0) || !std::isfinite(p->cell)) return set_err(LSLAM_ERR_ARG, "grid: cell must be > 0");
+    if (!(p->max_range > 0) || !std::isfinite(p->max_range) || !(p->max_range / p->cell <= 4096.0))
+        return set_err(LSLAM_ERR_ARG, "grid: max_range must be > 0, finite and at most 4096 cells");
+    if (p->grid_w < 16 || p->grid_w > 2048) return set_err(LSLAM_ERR_ARG, "grid: grid_w must be in [16, 2048]");
+    if (p->l_hit < 1 || p->l_hit > 1024) return set_err(LSLAM_ERR_ARG, "grid: l_hit must be in [1, 1024]");
+    if (p->l_miss < -1024 || p->l_miss > -1) return set_err(LSLAM_ERR_ARG, "grid: l_miss must be in [-1024, -1]");
+    if (p->l_min < -32768 || p->l_min >= 0) return set_err(LSLAM_ERR_ARG, "grid: l_min must be in [-32768, -1]");
+    if (p->l_max <= 0 || p->l_max > 32767) return set_err(LSLAM_ERR_ARG, "grid: l_max must be in [1, 32767]");
+    return LSLAM_OK;
+}
+
+template <int T, int WAVE_RAY>
+static int launch_grid_form(lslam_ctx *c, GridArgs &k) {
+    k.ntile = (k.grid_w + T - 1) / T;
+    const int64_t blocks = (int64_t)k.b.n_robots * k.ntile * k.ntile;
+    if (blocks >= ((int64_t)1 << 31)) return set_err(LSLAM_ERR_UNSUPPORTED, "grid: too many robots in one call");
+    static std::once_flag once;
+    std::call_once(once, [] { set_max_lds(grid_update_kernel<T, WAVE_RAY>); });
+    hipLaunchKernelGGL((grid_update_kernel<T, WAVE_RAY>), dim3((unsigned)blocks), dim3(GRID_TPB), grid_lds_bytes(T),
+                       c->stream, k);
+    HIPCHK(hipGetLastError());
+    return LSLAM_OK;
+}
+
+// One workgroup per (robot, tile).  LSLAM_GRID_FORM (tools/gridbench.py) selects the forms that were
+// measured and dropped: "128l", "64w", "128w" (tile side; a lane or a wave per ray); default "64l".
+static int launch_grid(lslam_ctx *c, const lslam_grid_batch *b, const lslam_grid_params *p) {
+    GridArgs k;
+    memset(&k, 0, sizeof(k));
+    k.b = *b;
+    k.inv = 1.0 / p->cell;
+    k.max_r2 = p->max_range * p->max_range;
+    k.grid_w = p->grid_w;
+    k.l_hit = p->l_hit;
+    k.l_miss = p->l_miss;
+    k.l_min = p->l_min;
+    k.l_max = p->l_max;
+    k.vec = (p->grid_w % 8 == 0 && ((uintptr_t)b->logodds & 15) == 0) ? 1 : 0;
+    int T = GRID_T, wave_ray = GRID_WAVE_RAY;
+    if (const char *e = getenv("LSLAM_GRID_FORM")) {
+        if (atoi(e) == 64 || atoi(e) == 128) T = atoi(e);
+        if (strchr(e, 'l')) wave_ray = 0;
+        if (strchr(e, 'w')) wave_ray = 1;
+    }
+    int st = timer_begin(c, LSLAM_K_GRID);
+    if (st) return st;
+    if (T == 128) st = wave_ray ? launch_grid_form<128, 1>(c, k) : launch_grid_form<128, 0>(c, k);
+    else st = wave_ray ? launch_grid_form<64, 1>(c, k) : launch_grid_form<64, 0>(c, k);
+    if (st) return st;
+    if ((st = timer_end(c, LSLAM_K_GRID))) return st;
+    const size_t R = (size_t)b->n_robots;
+    c->hz.outs.add(b->logodds, R * (size_t)p->grid_w * (size_t)p->grid_w * 2);
+    c->hz.outs.add(b->rot, R * 16);
+    c->hz.outs.add(b->n_used, R * 8);
+    c->hz.outs.add(b->flags, R * 4);
+    return LSLAM_OK;
+}
+
 // ---- express-scan codec (lslam_express.h) ----
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1000,6 +1062,25 @@ int lslam_scan_match(lslam_ctx *c, const lslam_match_batch *b, const lslam_match
     if (b->n_scans == 0) return LSLAM_OK;
     HIPCHK(hipSetDevice(c->device));
     return launch_match(c, b, p, u);
+}
+
+// On the main stream: every pipeline call ends there (its post pass and lane-group UKF run on it,
+// and it waits for ev_ukf when the UKF ran on the side stream), so a ukf_x given as pose is final.
+int lslam_grid_update(lslam_ctx *c, const lslam_grid_batch *b, const lslam_grid_params *p) {
+    int st = grid_check_params(p);
+    if (st) return st;
+    if (!b) return set_err(LSLAM_ERR_ARG, "grid: batch is NULL");
+    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "grid: negative n_robots");
+    if (b->n_robots > 0) {
+        if (!b->xy || !b->pt_off || !b->pose || !b->origin)
+            return set_err(LSLAM_ERR_ARG, "grid: missing input (xy, pt_off, pose, origin)");
+        if (!b->logodds || !b->rot || !b->n_used || !b->flags)
+            return set_err(LSLAM_ERR_ARG, "grid: missing output (logodds, rot, n_used, flags)");
+    }
+    if (!c) return set_err(LSLAM_ERR_ARG, "grid: ctx is NULL");
+    if (b->n_robots == 0) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return launch_grid(c, b, p);
 }
 
 int lslam_express_decode(lslam_ctx *c, const uint8_t *packets, int64_t n_packets, const lslam_express_measures *out) {

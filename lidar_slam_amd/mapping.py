@@ -1,0 +1,143 @@
+"""Occupancy-grid mapping: batched inverse-sensor-model updates (``lslam_grid_update``).
+
+The reference's GUI draws every measured point of the last revolution and forgets it
+(``mainWindow.py``, ``allSeries.replace``); the per-robot landmark list exists to feed ``hx``.
+``OccupancyGrid`` keeps the picture: per robot a square grid of clamped log-odds in HBM, updated
+from a revolution and the robot's pose.  Every beam is traced from the robot cell to its return;
+the cells it crosses become freer, the cell it ends in more occupied.  It chains onto
+``LandmarkMap``, whose posterior pose it reads on the device::
+
+    odo.step(xy, scan_chunk_off, chunk_pt_off, lm)       # writes lm.u
+    lm.step(xy, scan_chunk_off, chunk_pt_off)            # writes lm.x
+    grid.step(xy, scan_chunk_off, chunk_pt_off, pose=lm)  # reads lm.x and the points in place
+
+The definition (robot cell, integer ray, per-revolution sum, one clamp per call) is the comment on
+``lslam_grid_update`` in include/lidarslam.h; tests/occgrid_ref.py is its NumPy form and the kernel
+matches it bit for bit, given the (cos, sin) that the library wrote to ``rot``.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from . import _lib
+from .device import Context, DeviceArray
+from .odometry import _Grow
+from .slam import LandmarkMap, MapInput
+
+GRID_BAD_POSE, GRID_CLIPPED = _lib.GRID_BAD_POSE, _lib.GRID_CLIPPED
+TILE = 64  # cells a side of the kernel's tile (lslam_grid.h GRID_T): the tests place rays on its seams
+
+
+class OccupancyGrid:
+    """R robots' grids on one GPU.  ``params``: cell, max_range, grid_w, l_hit, l_miss, l_min, l_max
+    (``lslam_grid_params``; defaults 20 mm, 8000 mm, 512, 85, -41, -200, 350; log-odds in 0.01 nat).
+    ``origin`` [R, 2] (or one pair for all): the world coordinates of the corner of cell (0, 0);
+    default: every grid centred on (0, 0)."""
+
+    def __init__(self, ctx: Context, n_robots: int, origin=None, **params):
+        R = int(n_robots)
+        if R <= 0:
+            raise ValueError("n_robots must be > 0")
+        self.ctx, self.R = ctx, R
+        self.p = _lib.grid_params(**params)
+        self.W = int(self.p.grid_w)
+        half = 0.5 * self.W * self.p.cell
+        o = np.full((R, 2), -half) if origin is None else np.asarray(origin, np.float64)
+        self.origin_host = np.ascontiguousarray(np.broadcast_to(o, (R, 2)), np.float64)
+        # (a range error of params surfaces here, from the first call, before anything large is allocated)
+        _lib.check(_lib.load().lslam_grid_update(ctx.handle, C.byref(_lib.GridBatch()), C.byref(self.p)),
+                   "lslam_grid_update")
+        self.origin = ctx.to_device(self.origin_host)
+        self.logodds = ctx.empty((R, self.W, self.W), np.int16)
+        self.logodds.fill_zero()
+        self.rot = ctx.empty((R, 2), np.float64)
+        self.n_used = ctx.empty((R, 2), np.int32)
+        self.flags = ctx.empty(R, np.int32)
+        for a in (self.rot, self.n_used, self.flags):
+            a.fill_zero()
+        self._xy = _Grow(ctx, np.float64)
+        self._off = ctx.empty(R + 1, np.int32)  # (uploads are ordered on the stream: a step in flight keeps its own)
+        self._pose = ctx.empty((R, 3), np.float64)
+        self.steps = 0
+
+    @classmethod
+    def centred_on(cls, ctx, x0, **params):
+        """One grid per row of ``x0`` [R, >= 2] (start poses), each centred on its robot's start."""
+        x0 = np.asarray(x0, np.float64)
+        x0 = x0.reshape(-1, x0.shape[-1])
+        p = _lib.grid_params(**params)
+        return cls(ctx, len(x0), origin=x0[:, :2] - 0.5 * p.grid_w * p.cell, **params)
+
+    def step(self, xy, scan_chunk_off=None, chunk_pt_off=None, pose=None, sync=True):
+        """One revolution per robot, in the CSR layout of ``LandmarkMap.step`` / ``LidarOdometry.step``
+        (host array, ``DeviceArray`` or a ``MapInput``).  Device points are read in place: the call
+        is ordered on the context's stream, before whatever overwrites them later.  ``pose``
+        [R, 3] (x, y, theta): a host array, a float64 ``DeviceArray`` (``lm.x``) or a ``LandmarkMap``."""
+        ctx, R = self.ctx, self.R
+        if isinstance(xy, MapInput):
+            xy, scan_chunk_off, chunk_pt_off = xy.xy, xy.sco, xy.cpo
+        if pose is None:
+            raise ValueError("pose is required (host [R, 3], a DeviceArray or a LandmarkMap)")
+        sco = np.ascontiguousarray(scan_chunk_off, np.int64).reshape(-1)
+        cpo = np.ascontiguousarray(chunk_pt_off, np.int64).reshape(-1)
+        if sco.size != R + 1:
+            raise ValueError("one revolution per robot: scan_chunk_off needs n_robots + 1 entries")
+        off = cpo[sco]
+        p0, p1 = int(off[0]), int(off[-1])
+        if p0 < 0 or np.any(np.diff(off) < 0) or p1 >= 2 ** 31:
+            raise ValueError("inconsistent CSR offsets")
+        if isinstance(xy, DeviceArray):
+            if xy.dtype != np.float64 or xy.nbytes < 16 * p1:
+                raise ValueError("device xy must be float64 [n, 2] with n >= the last point offset")
+            dxy = xy
+        else:
+            h = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+            if h.shape[0] < p1:
+                raise ValueError("xy holds fewer points than chunk_pt_off describes")
+            dxy = self._xy.put_host(h[p0:p1])
+            off = off - p0
+        if isinstance(pose, LandmarkMap):
+            if pose.R != R:
+                raise ValueError("the map holds %d robots, the grid %d" % (pose.R, R))
+            pose = pose.x
+        if isinstance(pose, DeviceArray):
+            if pose.dtype != np.float64 or pose.nbytes < 24 * R:
+                raise ValueError("device pose must be float64 [n_robots, 3]")
+            dpose = pose
+        else:
+            hp = np.ascontiguousarray(pose, np.float64)
+            if hp.size != 3 * R:
+                raise ValueError("pose must hold n_robots x 3 values")
+            dpose = self._pose
+            dpose.upload_async(hp.reshape(R, 3))
+        doff = self._off
+        doff.upload_async(np.ascontiguousarray(off, np.int32))
+        b = _lib.GridBatch()
+        b.n_robots = R
+        b.xy, b.pt_off, b.pose, b.origin = dxy.addr, doff.addr, dpose.addr, self.origin.addr
+        b.logodds, b.rot, b.n_used, b.flags = self.logodds.addr, self.rot.addr, self.n_used.addr, self.flags.addr
+        _lib.check(_lib.load().lslam_grid_update(ctx.handle, C.byref(b), C.byref(self.p)), "lslam_grid_update")
+        self.steps += 1
+        if sync:
+            ctx.sync()
+
+    def results(self):
+        """logodds [R, W, W] int16 (row Y, 0.01 nat) and the last step's rot [R, 2], n_used [R, 2]
+        (points traced, valid points beyond max_range), flags [R]."""
+        return {"logodds": self.logodds.download(), "rot": self.rot.download(), "n_used": self.n_used.download(),
+                "flags": self.flags.download()}
+
+    def probability(self):
+        """Occupancy probability [R, W, W] on the host: 1 - 1 / (1 + exp(L / 100))."""
+        L = self.logodds.download().astype(np.float64)
+        return 1.0 - 1.0 / (1.0 + np.exp(L / 100.0))
+
+    def clear(self):
+        """Zero every grid (unknown everywhere), on the stream."""
+        self.logodds.fill_zero()
+
+    def upload(self, logodds):
+        """Replace the grids (tests, restarts): int16 [R, W, W]."""
+        self.logodds.upload(np.ascontiguousarray(logodds, np.int16).reshape(self.R, self.W, self.W))
