@@ -1718,10 +1718,11 @@ __device__ __forceinline__ void scan_body(const KArgs &a, const int s, unsigned 
         u[1] = B.ukf_u[2 * (size_t)s + 1];
         const int Lu = a.ukf.L;
         const double *lm = B.ukf_lmk + (size_t)s * 2 * Lu;
-        // no LMK_FROM_RANSAC here: this one-wave step runs stand-alone (lslam_ukf_step with
-        // LSLAM_UKF_MAP; no RANSAC in the call), and the fused pipeline never gives its post pass
-        // a non-map UKF (lslam_scan_pipeline sends it to ukf_group_kernel, whose origins are not
-        // capped by the LDS staging; checked on the host)
+        // not launched by any entry point: lslam_ukf_step without LSLAM_UKF_MAP runs
+        // ukf_group_kernel, with it build_args refuses the call (no association pass), and the
+        // fused pipeline never gives its post pass a non-map UKF (lslam_scan_pipeline sends it to
+        // ukf_group_kernel, whose origins are not capped by the LDS staging; checked on the host).
+        // The one-wave form runs as map mode's predict and update above.  No LMK_FROM_RANSAC here.
         auto lmk_fn = [&](int j, double &px, double &py) {
             px = lm[2 * j];
             py = lm[2 * j + 1];

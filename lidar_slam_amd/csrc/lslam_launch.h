@@ -1000,7 +1000,10 @@ static int ukf_step_impl(lslam_ctx *c, const lslam_scan_batch *b, const lslam_uk
     if (!bb.scan_chunk_off) return set_err(LSLAM_ERR_ARG, "scan_chunk_off required (may describe 0 chunks)");
     int st = build_args(k, &bb, nullptr, u, MODE_UKF, lds);
     if (st) return st;
-    const bool lanes = !(u->flags & LSLAM_UKF_MAP);  // MAP: the one-wave form (its post pass's step)
+    // always true here: build_args refuses LSLAM_UKF_MAP without the association pass (LSLAM_ERR_ARG
+    // above), so the stand-alone step is the lane-group form and the one-wave form runs only as map
+    // mode's post pass (tests/test_gpu_ukf_edges.py pins the refusal)
+    const bool lanes = !(u->flags & LSLAM_UKF_MAP);
     if ((u->flags & LSLAM_UKF_SIGMAS_IN) && !b->ukf_sigmas)
         return set_err(LSLAM_ERR_ARG, "LSLAM_UKF_SIGMAS_IN without ukf_sigmas");
     if ((b->ukf_sigmas || trace) && !lanes)

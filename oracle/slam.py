@@ -69,9 +69,11 @@ class RobotState:
         self.id_next = 0
 
 
-def map_step(rs: RobotState, xy, cpo, u, R_diag, predict=True, update=True, thr=20.0, trials=100, dt=oukf.DT):
+def map_step(rs: RobotState, xy, cpo, u, R_diag, predict=True, update=True, thr=20.0, trials=100, dt=oukf.DT,
+             meas_out=None):
     """One revolution (chunks cpo[k]:cpo[k+1] of xy) for one robot.
-    Returns (mask, models list)."""
+    Returns (mask, models list).  ``meas_out`` (a list) receives the update's measurement set:
+    per active slot (slot index, z (2,), matched landmark position (2,), the slot's R entries (2,))."""
     x, P = rs.x.copy(), rs.P.copy()
     f = oukf.UKF(1, dt=dt)
     f.x, f.P = x, P
@@ -103,5 +105,7 @@ def map_step(rs: RobotState, xy, cpo, u, R_diag, predict=True, update=True, thr=
         f.R = np.diag(Rd)
         z = np.concatenate([np.array(zz) for _, zz, _ in meas])
         f.update(z, [tuple(p) for _, _, p in meas])
+        if meas_out is not None:
+            meas_out.extend((k, tuple(zz), tuple(p), (R_diag[2 * k], R_diag[2 * k + 1])) for k, zz, p in meas)
     rs.x, rs.P = f.x, f.P
     return (np.concatenate(masks) if masks else np.zeros(0, np.uint8)), models

@@ -196,7 +196,8 @@ class UKF:
         self.P = self.P - np.dot(K, np.dot(S, K.T))
 
 
-def ukf_batch(x, P, u, z, lmk, R_diag, dt=DT, predict=True, update=True, Q=None, centred=True):
+def ukf_batch(x, P, u, z, lmk, R_diag, dt=DT, predict=True, update=True, Q=None, centred=True, alpha=1e-4, beta=2.0,
+              kappa=0.0):
     """Run one predict/update per scan; returns (x[S,3], P[S,3,3]).  ``centred=False``: filterpy's
     literal float64 means (state_mean / z_mean above) instead of the centred form."""
     S = x.shape[0]
@@ -205,7 +206,7 @@ def ukf_batch(x, P, u, z, lmk, R_diag, dt=DT, predict=True, update=True, Q=None,
     Po = np.zeros((S, 3, 3))
     means = {} if centred else dict(x_mean=state_mean, z_mean_fn=z_mean)
     for s in range(S):
-        f = UKF(L, dt=dt, **means)
+        f = UKF(L, dt=dt, alpha=alpha, beta=beta, kappa=kappa, **means)
         f.x = np.array(x[s], np.float64)
         f.P = np.array(P[s], np.float64).reshape(3, 3)
         f.R = np.diag(np.asarray(R_diag, np.float64))
@@ -220,3 +221,22 @@ def ukf_batch(x, P, u, z, lmk, R_diag, dt=DT, predict=True, update=True, Q=None,
         xo[s] = f.x
         Po[s] = f.P
     return xo, Po
+
+
+def update_sigma_bearings(x, P, u, lmk, dt=DT, predict=True, Q=None, alpha=1e-4, beta=2.0, kappa=0.0):
+    """The bearings hx gives the update's seven sigma points, [7][L] in (-pi, pi] (after the predict
+    unless ``predict`` is False)."""
+    f = UKF(len(lmk), dt=dt, alpha=alpha, beta=beta, kappa=kappa)
+    f.x, f.P = np.array(x, np.float64), np.array(P, np.float64).reshape(3, 3)
+    if Q is not None:
+        f.Q = np.asarray(Q, np.float64).reshape(3, 3)
+    if predict:
+        f.predict(np.asarray(u, np.float64))
+    else:
+        f.sigmas_f = f.points.sigma_points(f.x, f.P)
+    return np.array([transfer_function(s, [tuple(p) for p in lmk])[1::2] for s in f.sigmas_f])
+
+
+def straddles(bearings):
+    """Per landmark: the sigma bearings [7][L] lie on both sides of the +-pi cut."""
+    return (bearings.min(0) < -3.0) & (bearings.max(0) > 3.0)

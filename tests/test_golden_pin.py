@@ -18,7 +18,7 @@ from conftest import GOLDEN, ROOT
 REFERENCE_FIXTURES = ("assoc", "batch", "batch256", "big", "edge", "edge_chain", "express", "known", "live",
                       "mt_choice")
 GENERATORS = ("tests/golden/make_golden.py", "tests/golden/make_golden_express.py",
-              "tests/golden/make_ukf_exact.py", "tools/calibrate_twin.py")
+              "tests/golden/make_ukf_exact.py", "tests/golden/make_ukf_edges.py", "tools/calibrate_twin.py")
 
 
 @pytest.mark.parametrize("name", REFERENCE_FIXTURES)
