@@ -36,6 +36,8 @@
  *                         the wheel-speed input u of UKFMethods.py:17-24 made from the scans
  *   lslam_grid_update     nothing persistent: mainWindow.py draws the last revolution's points
  *                         (allSeries.replace) and forgets them; this keeps a log-odds map of them
+ *   lslam_map_match       nothing: the reference never reads a map back; this localises a revolution in
+ *                         the log-odds grid, the absolute correction that the grid makes possible
  */
 #ifndef LIDARSLAM_H
 #define LIDARSLAM_H
@@ -307,6 +309,48 @@ typedef struct lslam_grid_batch {
     int32_t *flags;         /* [n_robots] LSLAM_GRID_* */
 } lslam_grid_batch;
 
+/* ---- scan-to-map flags (lslam_mapmatch_batch.flags) ---- */
+enum {
+    LSLAM_MAPMATCH_EMPTY = 1,     /* a winning score of 0 (no valid point on an occupied cell): delta = 0, best = the centre */
+    LSLAM_MAPMATCH_EDGE = 2,      /* the winner lies on the search window's border along some axis */
+    LSLAM_MAPMATCH_BAD_POSE = 4,  /* as LSLAM_GRID_BAD_POSE: nothing is matched */
+    LSLAM_MAPMATCH_WEAK = 8       /* the winner's score is below the acceptance gate: pose_out = pose */
+};
+
+/* Scan-to-map matcher (lslam_map_match), 32 bytes.  The cell size and the map's width come from the
+ * lslam_grid_params given with the call. */
+typedef struct lslam_mapmatch_params {
+    double theta_step;    /* rotation step, rad (pi/360); > 0, finite */
+    int32_t win_w;        /* cells per side of the look-up window, even, 16..512 (512) */
+    int32_t smear;        /* smear radius, cells, 0..2 (2) */
+    int32_t k_trans;      /* translation half-window, cells, 0..15 (10): Nt = 2 k_trans + 1 */
+    int32_t k_theta;      /* rotation half-window, steps, 0..31 (20): Ntheta = 2 k_theta + 1 */
+    int32_t occ_min;      /* a map cell is occupied iff L >= occ_min; -32768..32767 (85: one hit) */
+    int32_t min_permille; /* acceptance gate, 0..1000 (500) */
+} lslam_mapmatch_params;
+
+/* One revolution per robot against the robot's grid, 112 bytes; all pointers DEVICE memory, all
+ * required but scores. */
+typedef struct lslam_mapmatch_batch {
+    int32_t n_robots;
+    int32_t reserved;
+    /* inputs */
+    const double *xy;         /* [pt_off[n_robots]][2] revolutions, each in its robot's frame */
+    const int32_t *pt_off;    /* [n_robots+1] CSR robot -> points */
+    const double *pose;       /* [n_robots][3] the guess (x mm, y mm, theta rad), e.g. the filter's ukf_x */
+    const double *origin;     /* [n_robots][2] world coordinates of the corner of cell (0, 0) */
+    const int16_t *logodds;   /* [n_robots][grid_w][grid_w], row Y: read only */
+    const double *rot;        /* [Ntheta][2] (cos, sin) of (k - k_theta) * theta_step: the caller's bits */
+    /* outputs */
+    double *pose_out;         /* [n_robots][3] the corrected pose, or the guess bit for bit; MAY ALIAS pose */
+    double *delta;            /* [n_robots][3] world-frame correction (dx mm, dy mm, dtheta rad) */
+    int32_t *best;            /* [n_robots][4] (k, jy, jx, score) of the winner */
+    int32_t *n_valid;         /* [n_robots][2] occupied cells in the window / valid points */
+    double *rot0;             /* [n_robots][2] (cos theta, sin theta) of the guess, as used */
+    int32_t *flags;           /* [n_robots] LSLAM_MAPMATCH_* */
+    int32_t *scores;          /* [n_robots][Ntheta][Nt][Nt] the whole score volume (optional) */
+} lslam_mapmatch_batch;
+
 typedef struct lslam_ctx lslam_ctx;  /* opaque: device, stream, events, scratch */
 
 /* ---- library / context ---- */
@@ -343,13 +387,15 @@ int lslam_abi_sizes(int64_t *sizes, int n);
 /* the same for the structs added since: lslam_grid_params, lslam_grid_batch.  Writes min(n, 2)
  * entries, returns 2. */
 int lslam_grid_abi_sizes(int64_t *sizes, int n);
+/* and for lslam_mapmatch_params, lslam_mapmatch_batch.  Writes min(n, 2) entries, returns 2. */
+int lslam_mapmatch_abi_sizes(int64_t *sizes, int n);
 /* per-kernel HIP-event timing on the ctx stream (kernel ids: LSLAM_K_*) */
 enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMARK = 3, LSLAM_K_UKF = 4,
        LSLAM_K_RNG = 5 /* parity-stream producer */, LSLAM_K_CONSENSUS = 6 /* per-chunk A4-A8 */,
        LSLAM_K_EXPRESS = 7 /* a whole express decode / scans call */,
        LSLAM_K_EXPRESS_SCATTER = 8 /* its decode + A1 + scatter kernel */,
        LSLAM_K_MATCH = 9 /* a whole scan-match call */, LSLAM_K_GRID = 10 /* a whole grid update */,
-       LSLAM_K_COUNT = 11 };
+       LSLAM_K_MAPMATCH = 11 /* a whole scan-to-map call */, LSLAM_K_COUNT = 12 };
 int lslam_set_timing(lslam_ctx *ctx, int enable);
 /* which kernel ids are timed while timing is on (bit k = LSLAM_K_k; default all).  Timing
  * events between the producer and consumer kernels change how the two streams overlap,
@@ -368,6 +414,7 @@ int lslam_ransac_params_default(lslam_ransac_params *p);
 int lslam_ukf_params_default(lslam_ukf_params *p, int32_t n_landmarks);
 int lslam_match_params_default(lslam_match_params *p);
 int lslam_grid_params_default(lslam_grid_params *p);
+int lslam_mapmatch_params_default(lslam_mapmatch_params *p);
 /* smallest e with RN(sqrt(e)) >= thr: (residual < thr) <=> (squared residual < cutoff) */
 double lslam_inlier_cutoff(double thr);
 /* MerweScaledSigmaPoints weights (filterpy _compute_weights) for n = 3 */
@@ -465,6 +512,45 @@ int lslam_scan_match(lslam_ctx *ctx, const lslam_match_batch *b, const lslam_mat
  * missing pointers return LSLAM_ERR_ARG (the message names the field), checked before the context
  * is touched; n_robots == 0 does nothing. */
 int lslam_grid_update(lslam_ctx *ctx, const lslam_grid_batch *b, const lslam_grid_params *p);
+/* Scan-to-map matching: one revolution per robot, a pose guess and the robot's log-odds grid -> the
+ * pose that best lays the revolution onto the occupied cells: the correlative search of
+ * lslam_scan_match with the map in the place of the previous revolution, in the world frame.  The
+ * grid's geometry is g's cell and grid_w (g is checked as lslam_grid_update checks it).  Per robot r,
+ * in FP64 with every operation rounded on its own, then integers; inv = 1.0 / cell, half = win_w/2,
+ * Nt = 2 k_trans + 1, Ntheta = 2 k_theta + 1:
+ *   0. robot cell: (px, py, theta) = pose[r], (ox, oy) = origin[r].  The library computes
+ *      (c, s) = (cos theta, sin theta) and writes them to rot0[r] (always, NaN for a non-finite
+ *      theta); the written bits are the definition's input.  X0 = floor((px - ox) inv),
+ *      Y0 = floor((py - oy) inv).  The pose is bad under the condition of lslam_grid_update step 0;
+ *      then flags[r] = LSLAM_MAPMATCH_BAD_POSE, delta = 0, best = (k_theta, k_trans, k_trans, 0),
+ *      n_valid = (0, 0), pose_out = pose bit for bit, and scores (if given) are zeros.
+ *   1. look-up grid G [win_w][win_w]: window cell (gy, gx) is map cell (Y0 - half + gy,
+ *      X0 - half + gx); it is occupied iff that cell lies in [0, grid_w)^2 and L >= occ_min.
+ *      G[c] = max(0, smear + 1 - Chebyshev distance from c to the nearest occupied window cell):
+ *      the smear is clipped to the window, as in lslam_scan_match step 1.  n_valid[r][0] = the number
+ *      of occupied window cells.
+ *   2. scores S[k][jy][jx] (int32): with (ck, sk) = rot[k], cc = c ck - s sk, ss = s ck + c sk.
+ *      Points are valid as in lslam_scan_match; there is no max_range cut.  For a valid point
+ *      wx = px + (cc x - ss y), wy = py + (ss x + cc y), X1 = floor((wx - ox) inv),
+ *      Y1 = floor((wy - oy) inv), ax = X1 - X0, ay = Y1 - Y0; the point counts iff both lie in
+ *      [-half - k_trans, half + k_trans) (compared as doubles).  S = the sum over those points of
+ *      G[ay + (jy - k_trans) + half][ax + (jx - k_trans) + half], 0 outside the window.
+ *      n_valid[r][1] = the number of valid points.
+ *   3. winner, parabola per axis, best, EMPTY and EDGE: steps 3-5 of lslam_scan_match.
+ *      delta = ((jx - k_trans + ox') cell, (jy - k_trans + oy') cell, (k - k_theta + ot') theta_step),
+ *      with the parabola offsets ox', oy', ot', is a world-frame correction of the guess.
+ *   4. gate, in int64: LSLAM_MAPMATCH_WEAK iff not EMPTY and
+ *      1000 score < min_permille (smear + 1) n_valid[r][1].
+ *   5. pose_out[r] = (px + delta[0], py + delta[1], theta + delta[2]), one addition each, no angle
+ *      wrap, iff none of EMPTY, BAD_POSE, WEAK is set; otherwise pose_out[r] = pose[r] bit for bit.
+ *      EDGE alone still applies the correction; delta and best are reported in every case.
+ *      pose_out may be pose itself: the thread that writes a robot's pose_out has read its pose.
+ * Runs on the context's main stream, after every earlier call: it sees the ukf_x of a preceding
+ * lslam_scan_pipeline and the grid of a preceding lslam_grid_update.  Out-of-range parameters and
+ * missing pointers return LSLAM_ERR_ARG (the message names the field), checked before the context
+ * is touched; n_robots == 0 does nothing. */
+int lslam_map_match(lslam_ctx *ctx, const lslam_mapmatch_batch *b, const lslam_grid_params *g,
+                    const lslam_mapmatch_params *m);
 
 #ifdef __cplusplus
 }

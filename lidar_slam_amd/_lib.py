@@ -29,9 +29,10 @@ CAPACITY, CHUNK_BOUND = 256, 512
 HYP_MT19937, HYP_PHILOX, HYP_EXPLICIT = 0, 1, 2
 UKF_PREDICT, UKF_UPDATE, UKF_LMK_FROM_RANSAC, UKF_MAP, UKF_SIGMAS_IN = 1, 2, 4, 8, 16
 K_POLAR, K_HYP, K_PIPELINE, K_LANDMARK, K_UKF, K_RNG, K_CONSENSUS = 0, 1, 2, 3, 4, 5, 6
-K_EXPRESS, K_EXPRESS_SCATTER, K_MATCH, K_GRID = 7, 8, 9, 10
+K_EXPRESS, K_EXPRESS_SCATTER, K_MATCH, K_GRID, K_MAPMATCH = 7, 8, 9, 10, 11
 MATCH_EMPTY, MATCH_EDGE = 1, 2
 GRID_BAD_POSE, GRID_CLIPPED = 1, 2
+MAPMATCH_EMPTY, MAPMATCH_EDGE, MAPMATCH_BAD_POSE, MAPMATCH_WEAK = 1, 2, 4, 8
 
 
 class HIPLibraryError(RuntimeError):
@@ -105,6 +106,17 @@ class GridBatch(C.Structure):
                [(n, _VP) for n in ("xy", "pt_off", "pose", "origin", "logodds", "rot", "n_used", "flags")]
 
 
+class MapMatchParams(C.Structure):
+    _fields_ = [("theta_step", C.c_double)] + \
+               [(n, C.c_int32) for n in ("win_w", "smear", "k_trans", "k_theta", "occ_min", "min_permille")]
+
+
+class MapMatchBatch(C.Structure):
+    _fields_ = [("n_robots", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, _VP) for n in ("xy", "pt_off", "pose", "origin", "logodds", "rot", "pose_out", "delta", "best",
+                                   "n_valid", "rot0", "flags", "scores")]
+
+
 assert C.sizeof(ChunkModel) == 112
 assert C.sizeof(LandmarkRec) == 56
 
@@ -119,6 +131,7 @@ EXPORTS = [
     "lslam_ukf_step", "lslam_ukf_trace", "lslam_scan_pipeline", "lslam_express_decode", "lslam_express_scans",
     "lslam_match_params_default", "lslam_scan_match",
     "lslam_grid_abi_sizes", "lslam_grid_params_default", "lslam_grid_update",
+    "lslam_mapmatch_abi_sizes", "lslam_mapmatch_params_default", "lslam_map_match",
 ]
 
 _lib = None
@@ -187,6 +200,9 @@ def load():
         "lslam_grid_abi_sizes": ([P(i64), C.c_int], C.c_int),
         "lslam_grid_params_default": ([P(GridParams)], C.c_int),
         "lslam_grid_update": ([_VP, P(GridBatch), P(GridParams)], C.c_int),
+        "lslam_mapmatch_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_mapmatch_params_default": ([P(MapMatchParams)], C.c_int),
+        "lslam_map_match": ([_VP, P(MapMatchBatch), P(GridParams), P(MapMatchParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -219,7 +235,10 @@ def _check_abi(L):
                                   ExpressRevs, MatchParams, MatchBatch)]
     got2 = (C.c_int64 * 2)()
     L.lslam_grid_abi_sizes(got2, 2)
-    got, want = list(got) + list(got2), want + [C.sizeof(GridParams), C.sizeof(GridBatch)]
+    got3 = (C.c_int64 * 2)()
+    L.lslam_mapmatch_abi_sizes(got3, 2)
+    got = list(got) + list(got2) + list(got3)
+    want = want + [C.sizeof(GridParams), C.sizeof(GridBatch), C.sizeof(MapMatchParams), C.sizeof(MapMatchBatch)]
     if list(got) != want:
         _err = HIPLibraryError("struct sizes differ between %s %s and the ctypes layouts %s"
                                % (LIB_PATH, list(got), want))
@@ -284,6 +303,14 @@ def match_params(**kw):
 def grid_params(**kw):
     p = GridParams()
     load().lslam_grid_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def mapmatch_params(**kw):
+    p = MapMatchParams()
+    load().lslam_mapmatch_params_default(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -6,7 +6,8 @@
 //   lslam_wave.h (wave primitives), lslam_rng.h / lslam_rng_pipe.h (MT19937, Philox, the
 //   stream parser), lslam_ransac.h (fits, residuals), lslam_ukf.h, lslam_express.h (the
 //   express-packet kernels), lslam_match.h (the scan matcher's two kernels), lslam_grid.h
-//   (the occupancy-grid kernel; its integer ray is lslam_grid_ray.h, plain C++);
+//   (the occupancy-grid kernel; its integer ray is lslam_grid_ray.h, plain C++), lslam_mapmatch.h
+//   (the scan-to-map matcher's two kernels);
 // the host side is included at the foot:
 //   lslam_hazards.h  which waits a call's producer needs (plain C++, no HIP)
 //   lslam_ctx.h      lslam_ctx, its grow-only device buffers and timers, create / destroy,
@@ -3047,6 +3048,8 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
 #include "lslam_match.h"
 // the occupancy-grid kernel, after those
 #include "lslam_grid.h"
+// the scan-to-map matcher's two kernels, last (they share lslam_match.h's device functions)
+#include "lslam_mapmatch.h"
 
 // ------------------------------------------------------------------------
 // host side: the context, then the launchers and entry points

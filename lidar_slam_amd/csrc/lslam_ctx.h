@@ -63,7 +63,7 @@ struct lslam_ctx {
     DevBuf scr;   // main-stream scratch: resolved draws (when the caller gives no draws_out)
     DevBuf escr;  // express-scan revolution builder scratch (per-packet flags/ranks, per-revolution info)
     DevBuf cscr;  // large-chunk consensus scratch: per-trial counts (+ Philox draws)
-    DevBuf mscr;  // scan-match score volume (when the caller gives no scores)
+    DevBuf mscr;  // score volume of a scan-match or scan-to-map call (when the caller gives no scores)
     int resolve_beside = 0;  // this call's resolves will likely run beside the next call's producer
     int n_cus = 1;           // compute units of the device
     uint32_t timing_mask = 0xffffffffu;  // kernel ids timed when timing is on (lslam_set_timing_mask)
@@ -368,6 +368,12 @@ int lslam_grid_abi_sizes(int64_t *sizes, int n) {
     return 2;
 }
 
+int lslam_mapmatch_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[2] = {(int64_t)sizeof(lslam_mapmatch_params), (int64_t)sizeof(lslam_mapmatch_batch)};
+    for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
+    return 2;
+}
+
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
     if (!c || (!dst && n)) return LSLAM_ERR_ARG;
     if (!n) return LSLAM_OK;
@@ -494,6 +500,19 @@ int lslam_grid_params_default(lslam_grid_params *p) {
     p->l_miss = -41;        // ln(0.4 / 0.6)
     p->l_min = -200;        // p ~ 0.12
     p->l_max = 350;         // p ~ 0.97
+    return LSLAM_OK;
+}
+
+int lslam_mapmatch_params_default(lslam_mapmatch_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->theta_step = LS_PI / 360.0;  // half a degree
+    p->win_w = 512;
+    p->smear = 2;
+    p->k_trans = 10;        // +-200 mm at 20 mm cells
+    p->k_theta = 20;        // +-10 degrees
+    p->occ_min = 85;        // one hit's worth of log-odds (lslam_grid_params.l_hit)
+    p->min_permille = 500;  // half of a perfect overlay
     return LSLAM_OK;
 }
 

@@ -889,6 +889,86 @@ static int launch_grid(lslam_ctx *c, const lslam_grid_batch *b, const lslam_grid
     return LSLAM_OK;
 }
 
+// ---- scan-to-map matcher (lslam_mapmatch.h) ----
+
+static int mapmatch_check_params(const lslam_mapmatch_params *m) {
+    if (!m) return set_err(LSLAM_ERR_ARG, "mapmatch: params is NULL");
+    if (!(m->theta_step > 0) || !std::isfinite(m->theta_step))
+        return set_err(LSLAM_ERR_ARG, "mapmatch: theta_step must be > 0");
+    if (m->win_w < 16 || m->win_w > 512 || (m->win_w & 1))
+        return set_err(LSLAM_ERR_ARG, "mapmatch: win_w must be even, in [16, 512]");
+    if (m->smear < 0 || m->smear > 2) return set_err(LSLAM_ERR_ARG, "mapmatch: smear must be in [0, 2]");
+    if (m->k_trans < 0 || m->k_trans > 15) return set_err(LSLAM_ERR_ARG, "mapmatch: k_trans must be in [0, 15]");
+    if (m->k_theta < 0 || m->k_theta > 31) return set_err(LSLAM_ERR_ARG, "mapmatch: k_theta must be in [0, 31]");
+    if (m->occ_min < -32768 || m->occ_min > 32767)
+        return set_err(LSLAM_ERR_ARG, "mapmatch: occ_min must be in [-32768, 32767]");
+    if (m->min_permille < 0 || m->min_permille > 1000)
+        return set_err(LSLAM_ERR_ARG, "mapmatch: min_permille must be in [0, 1000]");
+    return LSLAM_OK;
+}
+
+// mapmatch_search_kernel on a grid of (robots x rotation slices), then mapmatch_pick_kernel per
+// robot: the slice rule of launch_match (each slice reads the window and rebuilds G).
+static int launch_mapmatch(lslam_ctx *c, const lslam_mapmatch_batch *b, const lslam_grid_params *g,
+                           const lslam_mapmatch_params *m) {
+    MapMatchArgs k;
+    memset(&k, 0, sizeof(k));
+    k.b = *b;
+    k.cell = g->cell;
+    k.inv = 1.0 / g->cell;
+    k.theta_step = m->theta_step;
+    k.map_w = g->grid_w;
+    k.win_w = m->win_w;
+    k.half = m->win_w / 2;
+    k.smear = m->smear;
+    k.kt = m->k_trans;
+    k.kth = m->k_theta;
+    k.Nt = 2 * m->k_trans + 1;
+    k.Nth = 2 * m->k_theta + 1;
+    k.W = m->win_w + 2 * m->k_trans;
+    k.Sd = match_row_dwords(k.W);
+    k.occ_min = m->occ_min;
+    k.min_permille = m->min_permille;
+    k.vec = (g->grid_w % 8 == 0 && ((uintptr_t)b->logodds & 15) == 0) ? 1 : 0;
+    // LSLAM_MAPMATCH_FORM=cell (tools/mapmatchbench.py): the lane-per-cell window load on every map
+    if (const char *e = getenv("LSLAM_MAPMATCH_FORM"))
+        if (!strcmp(e, "cell")) k.vec = 0;
+    const int64_t want = 2 * (int64_t)c->n_cus;
+    int64_t ns = (want + b->n_robots - 1) / b->n_robots;
+    ns = std::min<int64_t>(std::max<int64_t>(ns, 1), k.Nth);
+    k.per_slice = (int)((k.Nth + ns - 1) / ns);
+    k.n_slices = (k.Nth + k.per_slice - 1) / k.per_slice;
+    if ((int64_t)b->n_robots * k.n_slices >= ((int64_t)1 << 31))
+        return set_err(LSLAM_ERR_UNSUPPORTED, "mapmatch: too many robots in one call");
+    const size_t vol = (size_t)b->n_robots * k.Nth * k.Nt * k.Nt * 4;
+    if (b->scores) {
+        k.scores = b->scores;
+    } else {
+        int st = c->mscr.ensure(c, vol, "mapmatch scores");
+        if (st) return st;
+        k.scores = c->mscr.as<int32_t>();
+    }
+    const int lds = mapmatch_lds_bytes(k.W, k.Sd, k.Nt);
+    static std::once_flag once;
+    std::call_once(once, [] { set_max_lds(mapmatch_search_kernel); });
+    int st = timer_begin(c, LSLAM_K_MAPMATCH);
+    if (st) return st;
+    hipLaunchKernelGGL(mapmatch_search_kernel, dim3((unsigned)(b->n_robots * k.n_slices)), dim3(MATCH_TPB), lds, c->stream, k);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(mapmatch_pick_kernel, dim3((unsigned)b->n_robots), dim3(MATCH_PICK_TPB), 0, c->stream, k);
+    HIPCHK(hipGetLastError());
+    if ((st = timer_end(c, LSLAM_K_MAPMATCH))) return st;
+    const size_t R = (size_t)b->n_robots;
+    c->hz.outs.add(b->pose_out, R * 24);
+    c->hz.outs.add(b->delta, R * 24);
+    c->hz.outs.add(b->best, R * 16);
+    c->hz.outs.add(b->n_valid, R * 8);
+    c->hz.outs.add(b->rot0, R * 16);
+    c->hz.outs.add(b->flags, R * 4);
+    c->hz.outs.add(b->scores, vol);
+    return LSLAM_OK;
+}
+
 // ---- express-scan codec (lslam_express.h) ----
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1084,6 +1164,27 @@ int lslam_grid_update(lslam_ctx *c, const lslam_grid_batch *b, const lslam_grid_
     if (b->n_robots == 0) return LSLAM_OK;
     HIPCHK(hipSetDevice(c->device));
     return launch_grid(c, b, p);
+}
+
+// On the main stream, as lslam_grid_update: a ukf_x given as pose is final, and so is the grid that
+// a preceding lslam_grid_update wrote.
+int lslam_map_match(lslam_ctx *c, const lslam_mapmatch_batch *b, const lslam_grid_params *g,
+                    const lslam_mapmatch_params *m) {
+    int st = mapmatch_check_params(m);
+    if (st) return st;
+    if ((st = grid_check_params(g))) return st;
+    if (!b) return set_err(LSLAM_ERR_ARG, "mapmatch: batch is NULL");
+    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "mapmatch: negative n_robots");
+    if (b->n_robots > 0) {
+        if (!b->xy || !b->pt_off || !b->pose || !b->origin || !b->logodds || !b->rot)
+            return set_err(LSLAM_ERR_ARG, "mapmatch: missing input (xy, pt_off, pose, origin, logodds, rot)");
+        if (!b->pose_out || !b->delta || !b->best || !b->n_valid || !b->rot0 || !b->flags)
+            return set_err(LSLAM_ERR_ARG, "mapmatch: missing output (pose_out, delta, best, n_valid, rot0, flags)");
+    }
+    if (!c) return set_err(LSLAM_ERR_ARG, "mapmatch: ctx is NULL");
+    if (b->n_robots == 0) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return launch_mapmatch(c, b, g, m);
 }
 
 int lslam_express_decode(lslam_ctx *c, const uint8_t *packets, int64_t n_packets, const lslam_express_measures *out) {
