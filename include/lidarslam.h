@@ -314,7 +314,10 @@ enum {
     LSLAM_MAPMATCH_EMPTY = 1,     /* a winning score of 0 (no valid point on an occupied cell): delta = 0, best = the centre */
     LSLAM_MAPMATCH_EDGE = 2,      /* the winner lies on the search window's border along some axis */
     LSLAM_MAPMATCH_BAD_POSE = 4,  /* as LSLAM_GRID_BAD_POSE: nothing is matched */
-    LSLAM_MAPMATCH_WEAK = 8       /* the winner's score is below the acceptance gate: pose_out = pose */
+    LSLAM_MAPMATCH_WEAK = 8,      /* the winner's score is below the acceptance gate: pose_out = pose */
+    /* lslam_map_fuse only, in the same word: */
+    LSLAM_MAPFUSE_OUTLIER = 16,   /* the innovation's Mahalanobis distance exceeds nis_max: no update */
+    LSLAM_MAPFUSE_BAD_COV = 32    /* P is not finite, or P + Rm is not positive definite: no update, nis = 0 */
 };
 
 /* Scan-to-map matcher (lslam_map_match), 32 bytes.  The cell size and the map's width come from the
@@ -350,6 +353,29 @@ typedef struct lslam_mapmatch_batch {
     int32_t *flags;           /* [n_robots] LSLAM_MAPMATCH_* */
     int32_t *scores;          /* [n_robots][Ntheta][Nt][Nt] the whole score volume (optional) */
 } lslam_mapmatch_batch;
+
+/* Match fusion (lslam_map_fuse), 24 bytes. */
+typedef struct lslam_mapfuse_params {
+    double r_scale;        /* factor on the match covariance Rm; finite, > 0 (1.0) */
+    double nis_max;        /* gate on the innovation's Mahalanobis distance; > 0, +inf: no gate (16.27: the
+                              99.9 % point of chi-square with 3 degrees of freedom) */
+    int32_t cut_permille;  /* candidates scoring above cut_permille / 1000 of the winner weigh in; 0..999 (900) */
+    int32_t reserved;
+} lslam_mapfuse_params;
+
+/* A scan-to-map match fused into the filter, 160 bytes: the match's batch with its fields and rules
+ * as they are (m.pose is the filter's mean and the search's guess, m.pose_out the updated mean,
+ * m.scores stays optional), then the covariance and the measurement; all pointers DEVICE memory, all
+ * required but m.scores and moments. */
+typedef struct lslam_mapfuse_batch {
+    lslam_mapmatch_batch m;
+    const double *P;          /* [n_robots][9] the filter's covariance, row-major, e.g. ukf_P */
+    double *P_out;            /* [n_robots][9] the updated covariance, or P bit for bit; MAY ALIAS P */
+    double *z;                /* [n_robots][3] the match as a measurement of the pose: pose + delta */
+    double *Rm;               /* [n_robots][9] its covariance, row-major */
+    double *nis;              /* [n_robots] the innovation's squared Mahalanobis distance */
+    int64_t *moments;         /* [n_robots][10] the integer moments of the score volume (optional) */
+} lslam_mapfuse_batch;
 
 typedef struct lslam_ctx lslam_ctx;  /* opaque: device, stream, events, scratch */
 
@@ -389,13 +415,16 @@ int lslam_abi_sizes(int64_t *sizes, int n);
 int lslam_grid_abi_sizes(int64_t *sizes, int n);
 /* and for lslam_mapmatch_params, lslam_mapmatch_batch.  Writes min(n, 2) entries, returns 2. */
 int lslam_mapmatch_abi_sizes(int64_t *sizes, int n);
+/* and for lslam_mapfuse_params, lslam_mapfuse_batch.  Writes min(n, 2) entries, returns 2. */
+int lslam_mapfuse_abi_sizes(int64_t *sizes, int n);
 /* per-kernel HIP-event timing on the ctx stream (kernel ids: LSLAM_K_*) */
 enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMARK = 3, LSLAM_K_UKF = 4,
        LSLAM_K_RNG = 5 /* parity-stream producer */, LSLAM_K_CONSENSUS = 6 /* per-chunk A4-A8 */,
        LSLAM_K_EXPRESS = 7 /* a whole express decode / scans call */,
        LSLAM_K_EXPRESS_SCATTER = 8 /* its decode + A1 + scatter kernel */,
        LSLAM_K_MATCH = 9 /* a whole scan-match call */, LSLAM_K_GRID = 10 /* a whole grid update */,
-       LSLAM_K_MAPMATCH = 11 /* a whole scan-to-map call */, LSLAM_K_COUNT = 12 };
+       LSLAM_K_MAPMATCH = 11 /* a whole scan-to-map call */, LSLAM_K_MAPFUSE = 12 /* a whole match-fusion call */,
+       LSLAM_K_COUNT = 13 };
 int lslam_set_timing(lslam_ctx *ctx, int enable);
 /* which kernel ids are timed while timing is on (bit k = LSLAM_K_k; default all).  Timing
  * events between the producer and consumer kernels change how the two streams overlap,
@@ -415,6 +444,7 @@ int lslam_ukf_params_default(lslam_ukf_params *p, int32_t n_landmarks);
 int lslam_match_params_default(lslam_match_params *p);
 int lslam_grid_params_default(lslam_grid_params *p);
 int lslam_mapmatch_params_default(lslam_mapmatch_params *p);
+int lslam_mapfuse_params_default(lslam_mapfuse_params *p);
 /* smallest e with RN(sqrt(e)) >= thr: (residual < thr) <=> (squared residual < cutoff) */
 double lslam_inlier_cutoff(double thr);
 /* MerweScaledSigmaPoints weights (filterpy _compute_weights) for n = 3 */
@@ -551,6 +581,50 @@ int lslam_grid_update(lslam_ctx *ctx, const lslam_grid_batch *b, const lslam_gri
  * is touched; n_robots == 0 does nothing. */
 int lslam_map_match(lslam_ctx *ctx, const lslam_mapmatch_batch *b, const lslam_grid_params *g,
                     const lslam_mapmatch_params *m);
+/* Match fusion: lslam_map_match as a measurement update of the filter.  The match is turned into a
+ * measurement z of the pose with a covariance Rm taken from the whole score volume, and (x, P) =
+ * (m.pose, P) is updated by a Kalman step, gated on the innovation's Mahalanobis distance under the
+ * filter's own uncertainty.  Per robot r:
+ *   0-4. steps 0-4 of lslam_map_match, verbatim, with b->m, g and m: robot cell, G, score volume S,
+ *      winner (k*, jy*, jx*, s0), parabola, delta, best, n_valid, rot0, EMPTY, EDGE, BAD_POSE, WEAK.
+ *      With EMPTY or BAD_POSE set, steps 5-7 are skipped and no further flag is set: moments, Rm and
+ *      nis are zeros, z = pose bit for bit.
+ *   5. moments, all int64: cut = (s0 cut_permille) div 1000.  Every candidate (k, jy, jx) of the
+ *      volume weighs w = max(0, S - cut) at the offsets a = jx - jx*, b = jy - jy*, c = k - k*;
+ *      moments[r] = (W = sum w, sum wa, sum wb, sum wc, sum waa, sum wab, sum wac, sum wbb, sum wbc,
+ *      sum wcc).  Integer sums do not depend on the order.  cut < s0, so W >= 1.  With scores below
+ *      2^31, |a|, |b| <= 30, |c| <= 62 and at most 63 * 31 * 31 candidates, every sum stays below
+ *      5e17 in magnitude, inside int64 and converted to double with one rounding.
+ *   6. match covariance, FP64, every operation rounded on its own.  Wd = (double)W; with the axes
+ *      (0, 1, 2) = (a, b, c): mean_i = (double)(sum w i) / Wd, and for i <= j
+ *      C_ij = (double)(sum w i j) / Wd - mean_i mean_j.  With sc = (cell, cell, theta_step):
+ *      Rm_ij = (C_ij sc_i) sc_j; on the diagonal Rm_ii = (C_ii sc_i) sc_i + (sc_i sc_i) / 12.0, the
+ *      variance of one search quantum, so that Rm is never singular; then Rm_ij = Rm_ij r_scale, and
+ *      Rm_ji = Rm_ij.  z = (px + delta[0], py + delta[1], theta + delta[2]), no angle wrap.
+ *   7. innovation and gate.  y = delta (the guess is the mean).  S_ij = P_ij + Rm_ij, all nine.  The
+ *      adjugate A of S, every entry of the form p q - r s (two products, one subtraction):
+ *        A00 = S11 S22 - S12 S21   A01 = S02 S21 - S01 S22   A02 = S01 S12 - S02 S11
+ *        A10 = S12 S20 - S10 S22   A11 = S00 S22 - S02 S20   A12 = S02 S10 - S00 S12
+ *        A20 = S10 S21 - S11 S20   A21 = S01 S20 - S00 S21   A22 = S00 S11 - S01 S10
+ *      det = (S00 A00 + S01 A10) + S02 A20.  LSLAM_MAPFUSE_BAD_COV iff some entry of P is not finite,
+ *      or not (S00 > 0 and A22 > 0 and det > 0 and det finite); then nis = 0.0 and the rest of this
+ *      step is skipped.  Otherwise Si_ij = A_ij / det, v_i = (Si_i0 y0 + Si_i1 y1) + Si_i2 y2,
+ *      nis = (y0 v0 + y1 v1) + y2 v2, and LSLAM_MAPFUSE_OUTLIER iff not (nis <= nis_max).
+ *   8. update, iff none of EMPTY, BAD_POSE, WEAK, BAD_COV, OUTLIER is set (EDGE alone still updates).
+ *      Every element of a 3x3 product is (t0 + t1) + t2.  K = P Si, K_ij = (P_i0 Si_0j + P_i1 Si_1j)
+ *      + P_i2 Si_2j.  pose_out_i = x_i + ((K_i0 y0 + K_i1 y1) + K_i2 y2).  Joseph form:
+ *      A = I - K (A_ij = 1.0 - K_ij on the diagonal, 0.0 - K_ij off it), AP = A P,
+ *      U_ij = (AP_i0 A_j0 + AP_i1 A_j1) + AP_i2 A_j2, KR = K Rm, V_ij = (KR_i0 K_j0 + KR_i1 K_j1)
+ *      + KR_i2 K_j2, T = U + V, P_out_ij = 0.5 (T_ij + T_ji).
+ *      In every other case pose_out and P_out are pose and P bit for bit (copied as 64-bit words: a
+ *      NaN keeps its payload).  delta, best, n_valid, rot0, flags, and for WEAK, OUTLIER and BAD_COV
+ *      also z, Rm, nis and moments are reported as computed.
+ * pose_out may be pose and P_out may be P: the one thread that writes a robot's outputs has read its
+ * pose and P first.  Runs on the context's main stream as lslam_map_match does.  Out-of-range
+ * parameters and missing pointers return LSLAM_ERR_ARG (the message names the field), checked before
+ * the context is touched; n_robots == 0 does nothing. */
+int lslam_map_fuse(lslam_ctx *ctx, const lslam_mapfuse_batch *b, const lslam_grid_params *g,
+                   const lslam_mapmatch_params *m, const lslam_mapfuse_params *f);
 
 #ifdef __cplusplus
 }

@@ -29,10 +29,11 @@ CAPACITY, CHUNK_BOUND = 256, 512
 HYP_MT19937, HYP_PHILOX, HYP_EXPLICIT = 0, 1, 2
 UKF_PREDICT, UKF_UPDATE, UKF_LMK_FROM_RANSAC, UKF_MAP, UKF_SIGMAS_IN = 1, 2, 4, 8, 16
 K_POLAR, K_HYP, K_PIPELINE, K_LANDMARK, K_UKF, K_RNG, K_CONSENSUS = 0, 1, 2, 3, 4, 5, 6
-K_EXPRESS, K_EXPRESS_SCATTER, K_MATCH, K_GRID, K_MAPMATCH = 7, 8, 9, 10, 11
+K_EXPRESS, K_EXPRESS_SCATTER, K_MATCH, K_GRID, K_MAPMATCH, K_MAPFUSE = 7, 8, 9, 10, 11, 12
 MATCH_EMPTY, MATCH_EDGE = 1, 2
 GRID_BAD_POSE, GRID_CLIPPED = 1, 2
 MAPMATCH_EMPTY, MAPMATCH_EDGE, MAPMATCH_BAD_POSE, MAPMATCH_WEAK = 1, 2, 4, 8
+MAPFUSE_OUTLIER, MAPFUSE_BAD_COV = 16, 32
 
 
 class HIPLibraryError(RuntimeError):
@@ -117,6 +118,14 @@ class MapMatchBatch(C.Structure):
                                    "n_valid", "rot0", "flags", "scores")]
 
 
+class MapFuseParams(C.Structure):
+    _fields_ = [("r_scale", C.c_double), ("nis_max", C.c_double), ("cut_permille", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MapFuseBatch(C.Structure):
+    _fields_ = [("m", MapMatchBatch)] + [(n, _VP) for n in ("P", "P_out", "z", "Rm", "nis", "moments")]
+
+
 assert C.sizeof(ChunkModel) == 112
 assert C.sizeof(LandmarkRec) == 56
 
@@ -132,6 +141,7 @@ EXPORTS = [
     "lslam_match_params_default", "lslam_scan_match",
     "lslam_grid_abi_sizes", "lslam_grid_params_default", "lslam_grid_update",
     "lslam_mapmatch_abi_sizes", "lslam_mapmatch_params_default", "lslam_map_match",
+    "lslam_mapfuse_abi_sizes", "lslam_mapfuse_params_default", "lslam_map_fuse",
 ]
 
 _lib = None
@@ -203,6 +213,9 @@ def load():
         "lslam_mapmatch_abi_sizes": ([P(i64), C.c_int], C.c_int),
         "lslam_mapmatch_params_default": ([P(MapMatchParams)], C.c_int),
         "lslam_map_match": ([_VP, P(MapMatchBatch), P(GridParams), P(MapMatchParams)], C.c_int),
+        "lslam_mapfuse_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_mapfuse_params_default": ([P(MapFuseParams)], C.c_int),
+        "lslam_map_fuse": ([_VP, P(MapFuseBatch), P(GridParams), P(MapMatchParams), P(MapFuseParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -237,8 +250,11 @@ def _check_abi(L):
     L.lslam_grid_abi_sizes(got2, 2)
     got3 = (C.c_int64 * 2)()
     L.lslam_mapmatch_abi_sizes(got3, 2)
-    got = list(got) + list(got2) + list(got3)
-    want = want + [C.sizeof(GridParams), C.sizeof(GridBatch), C.sizeof(MapMatchParams), C.sizeof(MapMatchBatch)]
+    got4 = (C.c_int64 * 2)()
+    L.lslam_mapfuse_abi_sizes(got4, 2)
+    got = list(got) + list(got2) + list(got3) + list(got4)
+    want = want + [C.sizeof(GridParams), C.sizeof(GridBatch), C.sizeof(MapMatchParams), C.sizeof(MapMatchBatch),
+                   C.sizeof(MapFuseParams), C.sizeof(MapFuseBatch)]
     if list(got) != want:
         _err = HIPLibraryError("struct sizes differ between %s %s and the ctypes layouts %s"
                                % (LIB_PATH, list(got), want))
@@ -311,6 +327,14 @@ def grid_params(**kw):
 def mapmatch_params(**kw):
     p = MapMatchParams()
     load().lslam_mapmatch_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def mapfuse_params(**kw):
+    p = MapFuseParams()
+    load().lslam_mapfuse_params_default(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -374,6 +374,12 @@ int lslam_mapmatch_abi_sizes(int64_t *sizes, int n) {
     return 2;
 }
 
+int lslam_mapfuse_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[2] = {(int64_t)sizeof(lslam_mapfuse_params), (int64_t)sizeof(lslam_mapfuse_batch)};
+    for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
+    return 2;
+}
+
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
     if (!c || (!dst && n)) return LSLAM_ERR_ARG;
     if (!n) return LSLAM_OK;
@@ -513,6 +519,15 @@ int lslam_mapmatch_params_default(lslam_mapmatch_params *p) {
     p->k_theta = 20;        // +-10 degrees
     p->occ_min = 85;        // one hit's worth of log-odds (lslam_grid_params.l_hit)
     p->min_permille = 500;  // half of a perfect overlay
+    return LSLAM_OK;
+}
+
+int lslam_mapfuse_params_default(lslam_mapfuse_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->r_scale = 1.0;
+    p->nis_max = 16.27;      // the 99.9 % point of chi-square with 3 degrees of freedom
+    p->cut_permille = 900;   // the candidates within a tenth of the winner's score
     return LSLAM_OK;
 }
 

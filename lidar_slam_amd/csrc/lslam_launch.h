@@ -907,11 +907,10 @@ static int mapmatch_check_params(const lslam_mapmatch_params *m) {
     return LSLAM_OK;
 }
 
-// mapmatch_search_kernel on a grid of (robots x rotation slices), then mapmatch_pick_kernel per
-// robot: the slice rule of launch_match (each slice reads the window and rebuilds G).
-static int launch_mapmatch(lslam_ctx *c, const lslam_mapmatch_batch *b, const lslam_grid_params *g,
-                           const lslam_mapmatch_params *m) {
-    MapMatchArgs k;
+// The kernels' arguments of a scan-to-map search (shared with launch_mapfuse): geometry, the slice
+// rule and the score volume, the caller's or the context's scratch; vol = its bytes.
+static int mapmatch_args(lslam_ctx *c, const lslam_mapmatch_batch *b, const lslam_grid_params *g,
+                         const lslam_mapmatch_params *m, MapMatchArgs &k, size_t &vol) {
     memset(&k, 0, sizeof(k));
     k.b = *b;
     k.cell = g->cell;
@@ -940,7 +939,7 @@ static int launch_mapmatch(lslam_ctx *c, const lslam_mapmatch_batch *b, const ls
     k.n_slices = (k.Nth + k.per_slice - 1) / k.per_slice;
     if ((int64_t)b->n_robots * k.n_slices >= ((int64_t)1 << 31))
         return set_err(LSLAM_ERR_UNSUPPORTED, "mapmatch: too many robots in one call");
-    const size_t vol = (size_t)b->n_robots * k.Nth * k.Nt * k.Nt * 4;
+    vol = (size_t)b->n_robots * k.Nth * k.Nt * k.Nt * 4;
     if (b->scores) {
         k.scores = b->scores;
     } else {
@@ -948,13 +947,28 @@ static int launch_mapmatch(lslam_ctx *c, const lslam_mapmatch_batch *b, const ls
         if (st) return st;
         k.scores = c->mscr.as<int32_t>();
     }
+    return LSLAM_OK;
+}
+
+static int launch_mapmatch_search(lslam_ctx *c, const MapMatchArgs &k) {
     const int lds = mapmatch_lds_bytes(k.W, k.Sd, k.Nt);
     static std::once_flag once;
     std::call_once(once, [] { set_max_lds(mapmatch_search_kernel); });
-    int st = timer_begin(c, LSLAM_K_MAPMATCH);
-    if (st) return st;
-    hipLaunchKernelGGL(mapmatch_search_kernel, dim3((unsigned)(b->n_robots * k.n_slices)), dim3(MATCH_TPB), lds, c->stream, k);
+    hipLaunchKernelGGL(mapmatch_search_kernel, dim3((unsigned)(k.b.n_robots * k.n_slices)), dim3(MATCH_TPB), lds, c->stream, k);
     HIPCHK(hipGetLastError());
+    return LSLAM_OK;
+}
+
+// mapmatch_search_kernel on a grid of (robots x rotation slices), then mapmatch_pick_kernel per
+// robot: the slice rule of launch_match (each slice reads the window and rebuilds G).
+static int launch_mapmatch(lslam_ctx *c, const lslam_mapmatch_batch *b, const lslam_grid_params *g,
+                           const lslam_mapmatch_params *m) {
+    MapMatchArgs k;
+    size_t vol;
+    int st = mapmatch_args(c, b, g, m, k, vol);
+    if (st) return st;
+    if ((st = timer_begin(c, LSLAM_K_MAPMATCH))) return st;
+    if ((st = launch_mapmatch_search(c, k))) return st;
     hipLaunchKernelGGL(mapmatch_pick_kernel, dim3((unsigned)b->n_robots), dim3(MATCH_PICK_TPB), 0, c->stream, k);
     HIPCHK(hipGetLastError());
     if ((st = timer_end(c, LSLAM_K_MAPMATCH))) return st;
@@ -966,6 +980,57 @@ static int launch_mapmatch(lslam_ctx *c, const lslam_mapmatch_batch *b, const ls
     c->hz.outs.add(b->rot0, R * 16);
     c->hz.outs.add(b->flags, R * 4);
     c->hz.outs.add(b->scores, vol);
+    return LSLAM_OK;
+}
+
+// ---- match fusion (lslam_mapfuse.h) ----
+
+static int mapfuse_check_params(const lslam_mapfuse_params *f) {
+    if (!f) return set_err(LSLAM_ERR_ARG, "mapfuse: params is NULL");
+    if (!(f->r_scale > 0) || !std::isfinite(f->r_scale))
+        return set_err(LSLAM_ERR_ARG, "mapfuse: r_scale must be > 0 and finite");
+    if (!(f->nis_max > 0)) return set_err(LSLAM_ERR_ARG, "mapfuse: nis_max must be > 0 (+inf: no gate)");
+    if (f->cut_permille < 0 || f->cut_permille > 999)
+        return set_err(LSLAM_ERR_ARG, "mapfuse: cut_permille must be in [0, 999]");
+    return LSLAM_OK;
+}
+
+// mapmatch_search_kernel as launch_mapmatch launches it (the same slice rule, the same scratch
+// volume), then mapfuse_pick_kernel per robot.
+static int launch_mapfuse(lslam_ctx *c, const lslam_mapfuse_batch *b, const lslam_grid_params *g,
+                          const lslam_mapmatch_params *m, const lslam_mapfuse_params *f) {
+    MapFuseArgs k;
+    memset(&k, 0, sizeof(k));
+    size_t vol;
+    int st = mapmatch_args(c, &b->m, g, m, k.m, vol);
+    if (st) return st;
+    k.P = b->P;
+    k.P_out = b->P_out;
+    k.z = b->z;
+    k.Rm = b->Rm;
+    k.nis = b->nis;
+    k.moments = b->moments;
+    k.r_scale = f->r_scale;
+    k.nis_max = f->nis_max;
+    k.cut_permille = f->cut_permille;
+    if ((st = timer_begin(c, LSLAM_K_MAPFUSE))) return st;
+    if ((st = launch_mapmatch_search(c, k.m))) return st;
+    hipLaunchKernelGGL(mapfuse_pick_kernel<0>, dim3((unsigned)b->m.n_robots), dim3(MATCH_PICK_TPB), 0, c->stream, k);
+    HIPCHK(hipGetLastError());
+    if ((st = timer_end(c, LSLAM_K_MAPFUSE))) return st;
+    const size_t R = (size_t)b->m.n_robots;
+    c->hz.outs.add(b->m.pose_out, R * 24);
+    c->hz.outs.add(b->m.delta, R * 24);
+    c->hz.outs.add(b->m.best, R * 16);
+    c->hz.outs.add(b->m.n_valid, R * 8);
+    c->hz.outs.add(b->m.rot0, R * 16);
+    c->hz.outs.add(b->m.flags, R * 4);
+    c->hz.outs.add(b->m.scores, vol);
+    c->hz.outs.add(b->P_out, R * 72);
+    c->hz.outs.add(b->z, R * 24);
+    c->hz.outs.add(b->Rm, R * 72);
+    c->hz.outs.add(b->nis, R * 8);
+    c->hz.outs.add(b->moments, R * 80);
     return LSLAM_OK;
 }
 
@@ -1185,6 +1250,29 @@ int lslam_map_match(lslam_ctx *c, const lslam_mapmatch_batch *b, const lslam_gri
     if (b->n_robots == 0) return LSLAM_OK;
     HIPCHK(hipSetDevice(c->device));
     return launch_mapmatch(c, b, g, m);
+}
+
+// On the main stream, as lslam_map_match.
+int lslam_map_fuse(lslam_ctx *c, const lslam_mapfuse_batch *b, const lslam_grid_params *g,
+                   const lslam_mapmatch_params *m, const lslam_mapfuse_params *f) {
+    int st = mapmatch_check_params(m);
+    if (st) return st;
+    if ((st = grid_check_params(g))) return st;
+    if ((st = mapfuse_check_params(f))) return st;
+    if (!b) return set_err(LSLAM_ERR_ARG, "mapfuse: batch is NULL");
+    if (b->m.n_robots < 0) return set_err(LSLAM_ERR_ARG, "mapfuse: negative n_robots");
+    if (b->m.n_robots > 0) {
+        if (!b->m.xy || !b->m.pt_off || !b->m.pose || !b->m.origin || !b->m.logodds || !b->m.rot || !b->P)
+            return set_err(LSLAM_ERR_ARG, "mapfuse: missing input (xy, pt_off, pose, origin, logodds, rot, P)");
+        if (!b->m.pose_out || !b->m.delta || !b->m.best || !b->m.n_valid || !b->m.rot0 || !b->m.flags || !b->P_out ||
+            !b->z || !b->Rm || !b->nis)
+            return set_err(LSLAM_ERR_ARG,
+                           "mapfuse: missing output (pose_out, delta, best, n_valid, rot0, flags, P_out, z, Rm, nis)");
+    }
+    if (!c) return set_err(LSLAM_ERR_ARG, "mapfuse: ctx is NULL");
+    if (b->m.n_robots == 0) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return launch_mapfuse(c, b, g, m, f);
 }
 
 int lslam_express_decode(lslam_ctx *c, const uint8_t *packets, int64_t n_packets, const lslam_express_measures *out) {
