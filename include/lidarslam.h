@@ -38,6 +38,7 @@
  *                         (allSeries.replace) and forgets them; this keeps a log-odds map of them
  *   lslam_map_match       nothing: the reference never reads a map back; this localises a revolution in
  *                         the log-odds grid, the absolute correction that the grid makes possible
+ *   lslam_map_relocalize  nothing: the same, without a pose guess (a restart in a stored grid)
  */
 #ifndef LIDARSLAM_H
 #define LIDARSLAM_H
@@ -377,6 +378,57 @@ typedef struct lslam_mapfuse_batch {
     int64_t *moments;         /* [n_robots][10] the integer moments of the score volume (optional) */
 } lslam_mapfuse_batch;
 
+/* ---- relocalisation flags (lslam_reloc_batch.flags) ---- */
+enum {
+    LSLAM_RELOC_LOST = 1,       /* no candidate passed the fine matcher's gates: pose_out untouched */
+    LSLAM_RELOC_AMBIGUOUS = 2   /* a second, distinct pose scores within ambig_permille of the winner: pose_out untouched */
+};
+
+/* Global relocalisation (lslam_map_relocalize), 56 bytes. */
+typedef struct lslam_reloc_params {
+    double head_step;          /* heading step of the coarse search, rad (2 pi / 180); > 0, finite */
+    double dup_mm;             /* two refined poses this close along x and y ... ; >= 0 (100.0) */
+    double dup_rad;            /* ... and in heading are one pose; >= 0 (0.0873) */
+    double reset_sigma_xy;     /* P_out of a found robot: diag(sxy^2, sxy^2, sth^2); > 0, finite (50.0 mm) */
+    double reset_sigma_theta;  /* > 0, finite (0.05 rad) */
+    int32_t n_head;            /* headings of the coarse search, 4..1024 (180) */
+    int32_t factor;            /* fine cells per coarse cell and side: 2, 4 or 8, a divisor of grid_w with
+                                  grid_w / factor in 4..256 (4) */
+    int32_t n_cand;            /* K, coarse peaks refined by the fine matcher, 1..16 (8) */
+    int32_t ambig_permille;    /* a rival at this share of the winner's fine score is an ambiguity, 0..1000 (900) */
+} lslam_reloc_params;
+
+/* One revolution per robot against the robot's grid, no pose guess, 176 bytes; all pointers DEVICE
+ * memory, all required but P_out and coarse_scores.  K = n_cand, Wc = grid_w / factor. */
+typedef struct lslam_reloc_batch {
+    int32_t n_robots;
+    int32_t reserved;
+    /* inputs */
+    const double *xy;         /* [pt_off[n_robots]][2] revolutions, each in its robot's frame */
+    const int32_t *pt_off;    /* [n_robots+1] CSR robot -> points */
+    const double *origin;     /* [n_robots][2] world coordinates of the corner of cell (0, 0) */
+    const int16_t *logodds;   /* [n_robots][grid_w][grid_w], row Y: read only */
+    const double *rot;        /* [Ntheta][2] the fine matcher's table, as lslam_mapmatch_batch.rot */
+    const double *head_rot;   /* [n_head][2] (cos, sin) of k * head_step: the caller's bits */
+    /* outputs */
+    int32_t *n_occ;           /* [n_robots] occupied coarse cells */
+    int32_t *n_used;          /* [n_robots] valid points within max_range */
+    int32_t *cand;            /* [K][n_robots][4] (k, ty, tx, coarse score) of rank j; (-1, -1, -1, 0) if missing */
+    double *cand_pose;        /* [K][n_robots][3] the pose of rank j's coarse cell; quiet NaNs if missing */
+    double *fine_pose;        /* [K][n_robots][3] lslam_map_match's pose_out from cand_pose[j] */
+    double *fine_delta;       /* [K][n_robots][3] its delta */
+    int32_t *fine_best;       /* [K][n_robots][4] its best */
+    int32_t *fine_nvalid;     /* [K][n_robots][2] its n_valid */
+    double *fine_rot0;        /* [K][n_robots][2] its rot0 */
+    int32_t *fine_flags;      /* [K][n_robots] its flags */
+    int32_t *result;          /* [n_robots][8] winner rank, its k, ty, tx, coarse score, fine score, best rival's
+                                 rank or -1, that rival's fine score or 0 */
+    int32_t *flags;           /* [n_robots] LSLAM_RELOC_* */
+    double *pose_out;         /* [n_robots][3] written for a found, unambiguous robot only, e.g. ukf_x */
+    double *P_out;            /* [n_robots][9] the same (optional), e.g. ukf_P */
+    int32_t *coarse_scores;   /* [n_robots][n_head][Wc][Wc] the whole coarse volume (optional) */
+} lslam_reloc_batch;
+
 typedef struct lslam_ctx lslam_ctx;  /* opaque: device, stream, events, scratch */
 
 /* ---- library / context ---- */
@@ -417,6 +469,8 @@ int lslam_grid_abi_sizes(int64_t *sizes, int n);
 int lslam_mapmatch_abi_sizes(int64_t *sizes, int n);
 /* and for lslam_mapfuse_params, lslam_mapfuse_batch.  Writes min(n, 2) entries, returns 2. */
 int lslam_mapfuse_abi_sizes(int64_t *sizes, int n);
+/* and for lslam_reloc_params, lslam_reloc_batch.  Writes min(n, 2) entries, returns 2. */
+int lslam_reloc_abi_sizes(int64_t *sizes, int n);
 /* per-kernel HIP-event timing on the ctx stream (kernel ids: LSLAM_K_*) */
 enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMARK = 3, LSLAM_K_UKF = 4,
        LSLAM_K_RNG = 5 /* parity-stream producer */, LSLAM_K_CONSENSUS = 6 /* per-chunk A4-A8 */,
@@ -424,7 +478,7 @@ enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMAR
        LSLAM_K_EXPRESS_SCATTER = 8 /* its decode + A1 + scatter kernel */,
        LSLAM_K_MATCH = 9 /* a whole scan-match call */, LSLAM_K_GRID = 10 /* a whole grid update */,
        LSLAM_K_MAPMATCH = 11 /* a whole scan-to-map call */, LSLAM_K_MAPFUSE = 12 /* a whole match-fusion call */,
-       LSLAM_K_COUNT = 13 };
+       LSLAM_K_RELOC = 13 /* a whole relocalisation call */, LSLAM_K_COUNT = 14 };
 int lslam_set_timing(lslam_ctx *ctx, int enable);
 /* which kernel ids are timed while timing is on (bit k = LSLAM_K_k; default all).  Timing
  * events between the producer and consumer kernels change how the two streams overlap,
@@ -437,6 +491,11 @@ int lslam_timing_reset(lslam_ctx *ctx);
  * (C5) and whose steps exceed it runs the producer in epochs of as many draws as fit, each
  * resolved before its slot is reused.  bytes <= 0 restores the default.  Syncs. */
 int lslam_set_steps_budget(lslam_ctx *ctx, int64_t bytes);
+/* Bytes of coarse-score scratch of a relocalisation call (default: the score volume of a 4096-robot
+ * map match at its defaults, 296 MB, or the LSLAM_RELOC_BUDGET environment variable).  A call whose
+ * coarse volumes exceed it runs its coarse stage in chunks of as many robots as fit (at least one);
+ * the results do not depend on it.  bytes <= 0 restores the default. */
+int lslam_set_reloc_budget(lslam_ctx *ctx, int64_t bytes);
 
 /* ---- host helpers ---- */
 int lslam_ransac_params_default(lslam_ransac_params *p);
@@ -445,6 +504,7 @@ int lslam_match_params_default(lslam_match_params *p);
 int lslam_grid_params_default(lslam_grid_params *p);
 int lslam_mapmatch_params_default(lslam_mapmatch_params *p);
 int lslam_mapfuse_params_default(lslam_mapfuse_params *p);
+int lslam_reloc_params_default(lslam_reloc_params *p);
 /* smallest e with RN(sqrt(e)) >= thr: (residual < thr) <=> (squared residual < cutoff) */
 double lslam_inlier_cutoff(double thr);
 /* MerweScaledSigmaPoints weights (filterpy _compute_weights) for n = 3 */
@@ -625,6 +685,60 @@ int lslam_map_match(lslam_ctx *ctx, const lslam_mapmatch_batch *b, const lslam_g
  * the context is touched; n_robots == 0 does nothing. */
 int lslam_map_fuse(lslam_ctx *ctx, const lslam_mapfuse_batch *b, const lslam_grid_params *g,
                    const lslam_mapmatch_params *m, const lslam_mapfuse_params *f);
+
+/* Global relocalisation: one revolution per robot and the robot's log-odds grid, NO pose guess -> the
+ * pose in the whole grid, over all headings, that best lays the revolution onto the map; LOST if there
+ * is none, AMBIGUOUS if there are two.  A coarse correlative search over every coarse cell and every
+ * heading, the K best separated peaks refined by lslam_map_match, then a selection.  g and m are
+ * checked as lslam_map_match checks them, q as its table says; the fine window must cover one coarse
+ * quantum: 2 m.k_trans >= q.factor and 2 m.k_theta m.theta_step >= q.head_step.  Per robot r, in FP64
+ * with every operation rounded on its own, then integers; f = q.factor, Wc = grid_w / f,
+ * cellc = cell f, invc = 1.0 / cellc, K = q.n_cand:
+ *   0. coarse map: C[cy][cx] = 1 iff some fine cell of the f x f block (rows f cy .. f cy + f - 1,
+ *      likewise columns) holds L >= m.occ_min.  n_occ[r] = the number of set coarse cells.
+ *   1. points: valid as in lslam_scan_match (both coordinates finite, not exactly (0, 0)); only valid
+ *      points with x x + y y <= max_range max_range are used (lslam_grid_update step 1).
+ *      n_used[r] = their count.
+ *   2. coarse scores Sc[k][ty][tx] (int32), k in [0, n_head), ty, tx in [0, Wc): with
+ *      (c, s) = head_rot[k], the caller's bits for the heading (double)k head_step, for each used
+ *      point x' = c x - s y, y' = s x + c y, ax = floor(x' invc + 0.5), ay = floor(y' invc + 0.5);
+ *      the point counts iff -Wc < ax < Wc and -Wc < ay < Wc (compared as doubles).  Sc = the sum over
+ *      those points of C[ty + ay][tx + ax], 0 outside the coarse grid: the robot at the centre of
+ *      coarse cell (ty, tx).
+ *   3. peaks: candidates are ordered by score, highest first, then by the smaller flat index
+ *      (k Wc + ty) Wc + tx.  A candidate is a peak iff its score is > 0 and it comes before all of its
+ *      up to 26 neighbours in that order; heading neighbours are k +- 1 mod n_head, translation
+ *      neighbours outside the coarse grid do not exist.  The first K peaks in that order are the
+ *      candidates j = 0 .. K-1: cand[j][r] = (k, ty, tx, score), cand_pose[j][r] =
+ *      (ox + ((double)tx + 0.5) cellc, oy + ((double)ty + 0.5) cellc, (double)k head_step).  Missing
+ *      ranks get cand = (-1, -1, -1, 0) and a pose of three quiet NaNs.  The layout is [K][n_robots],
+ *      so rank j is a plain [n_robots][3] pose array.
+ *   4. fine stage: for each rank j, lslam_map_match steps 0-5 exactly as written, with
+ *      pose = cand_pose[j], the robot's grid and origin, and m; its outputs go to fine_pose[j],
+ *      fine_delta[j], fine_best[j], fine_nvalid[j], fine_rot0[j], fine_flags[j].  A NaN pose gives
+ *      BAD_POSE by that definition's rule.
+ *   5. selection: rank j is eligible iff fine_flags[j] & (EMPTY | BAD_POSE | WEAK) == 0.  The winner
+ *      is the eligible rank with the highest fine_best[j][3], then the lowest j.  With no eligible
+ *      rank flags[r] = LSLAM_RELOC_LOST.  A rival is an eligible rank other than the winner that is
+ *      not a duplicate of it: with the refined poses a and b, dt = fabs(a.theta - b.theta), and
+ *      dt = two_pi - dt if dt > pi (the double literals 3.141592653589793 and 6.283185307179586); the
+ *      rank is a duplicate iff fabs(a.x - b.x) <= dup_mm, fabs(a.y - b.y) <= dup_mm and dt <= dup_rad.
+ *      The best rival is the one with the highest fine score, then the lowest j.
+ *      LSLAM_RELOC_AMBIGUOUS iff some rival has 1000 score_rival >= ambig_permille score_winner (int64).
+ *      result[r] = (winner rank, its k, ty, tx, its coarse score, its fine score, the best rival's
+ *      rank or -1, that rival's fine score or 0); with LOST (-1, -1, -1, -1, 0, 0, -1, 0).
+ *   6. outputs: iff neither LOST nor AMBIGUOUS, pose_out[r] = the winner's fine_pose, three doubles
+ *      copied bit for bit, and (if P_out is given) P_out[r] = diag(sxy sxy, sxy sxy, sth sth) from
+ *      reset_sigma_xy and reset_sigma_theta, the products taken once on the host, zeros off the
+ *      diagonal.  Otherwise pose_out[r] and P_out[r] keep their bits.  pose_out may be the filter's
+ *      ukf_x and P_out its ukf_P.
+ * coarse_scores, if given, receives Sc.  The coarse volume is otherwise held in a scratch of bounded
+ * size and the robots go through the coarse stage in chunks (lslam_set_reloc_budget); no result
+ * depends on that.  Runs on the context's main stream as lslam_map_match does.  Out-of-range
+ * parameters and missing pointers return LSLAM_ERR_ARG (the message names the field), checked before
+ * the context is touched; n_robots == 0 does nothing. */
+int lslam_map_relocalize(lslam_ctx *ctx, const lslam_reloc_batch *b, const lslam_grid_params *g,
+                         const lslam_mapmatch_params *m, const lslam_reloc_params *q);
 
 #ifdef __cplusplus
 }

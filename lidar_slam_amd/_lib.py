@@ -29,11 +29,12 @@ CAPACITY, CHUNK_BOUND = 256, 512
 HYP_MT19937, HYP_PHILOX, HYP_EXPLICIT = 0, 1, 2
 UKF_PREDICT, UKF_UPDATE, UKF_LMK_FROM_RANSAC, UKF_MAP, UKF_SIGMAS_IN = 1, 2, 4, 8, 16
 K_POLAR, K_HYP, K_PIPELINE, K_LANDMARK, K_UKF, K_RNG, K_CONSENSUS = 0, 1, 2, 3, 4, 5, 6
-K_EXPRESS, K_EXPRESS_SCATTER, K_MATCH, K_GRID, K_MAPMATCH, K_MAPFUSE = 7, 8, 9, 10, 11, 12
+K_EXPRESS, K_EXPRESS_SCATTER, K_MATCH, K_GRID, K_MAPMATCH, K_MAPFUSE, K_RELOC = 7, 8, 9, 10, 11, 12, 13
 MATCH_EMPTY, MATCH_EDGE = 1, 2
 GRID_BAD_POSE, GRID_CLIPPED = 1, 2
 MAPMATCH_EMPTY, MAPMATCH_EDGE, MAPMATCH_BAD_POSE, MAPMATCH_WEAK = 1, 2, 4, 8
 MAPFUSE_OUTLIER, MAPFUSE_BAD_COV = 16, 32
+RELOC_LOST, RELOC_AMBIGUOUS = 1, 2
 
 
 class HIPLibraryError(RuntimeError):
@@ -126,6 +127,18 @@ class MapFuseBatch(C.Structure):
     _fields_ = [("m", MapMatchBatch)] + [(n, _VP) for n in ("P", "P_out", "z", "Rm", "nis", "moments")]
 
 
+class RelocParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("head_step", "dup_mm", "dup_rad", "reset_sigma_xy", "reset_sigma_theta")] + \
+               [(n, C.c_int32) for n in ("n_head", "factor", "n_cand", "ambig_permille")]
+
+
+class RelocBatch(C.Structure):
+    _fields_ = [("n_robots", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, _VP) for n in ("xy", "pt_off", "origin", "logodds", "rot", "head_rot", "n_occ", "n_used", "cand",
+                                   "cand_pose", "fine_pose", "fine_delta", "fine_best", "fine_nvalid", "fine_rot0",
+                                   "fine_flags", "result", "flags", "pose_out", "P_out", "coarse_scores")]
+
+
 assert C.sizeof(ChunkModel) == 112
 assert C.sizeof(LandmarkRec) == 56
 
@@ -142,6 +155,7 @@ EXPORTS = [
     "lslam_grid_abi_sizes", "lslam_grid_params_default", "lslam_grid_update",
     "lslam_mapmatch_abi_sizes", "lslam_mapmatch_params_default", "lslam_map_match",
     "lslam_mapfuse_abi_sizes", "lslam_mapfuse_params_default", "lslam_map_fuse",
+    "lslam_reloc_abi_sizes", "lslam_reloc_params_default", "lslam_map_relocalize", "lslam_set_reloc_budget",
 ]
 
 _lib = None
@@ -216,6 +230,10 @@ def load():
         "lslam_mapfuse_abi_sizes": ([P(i64), C.c_int], C.c_int),
         "lslam_mapfuse_params_default": ([P(MapFuseParams)], C.c_int),
         "lslam_map_fuse": ([_VP, P(MapFuseBatch), P(GridParams), P(MapMatchParams), P(MapFuseParams)], C.c_int),
+        "lslam_reloc_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_reloc_params_default": ([P(RelocParams)], C.c_int),
+        "lslam_map_relocalize": ([_VP, P(RelocBatch), P(GridParams), P(MapMatchParams), P(RelocParams)], C.c_int),
+        "lslam_set_reloc_budget": ([_VP, i64], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -252,9 +270,11 @@ def _check_abi(L):
     L.lslam_mapmatch_abi_sizes(got3, 2)
     got4 = (C.c_int64 * 2)()
     L.lslam_mapfuse_abi_sizes(got4, 2)
-    got = list(got) + list(got2) + list(got3) + list(got4)
+    got5 = (C.c_int64 * 2)()
+    L.lslam_reloc_abi_sizes(got5, 2)
+    got = list(got) + list(got2) + list(got3) + list(got4) + list(got5)
     want = want + [C.sizeof(GridParams), C.sizeof(GridBatch), C.sizeof(MapMatchParams), C.sizeof(MapMatchBatch),
-                   C.sizeof(MapFuseParams), C.sizeof(MapFuseBatch)]
+                   C.sizeof(MapFuseParams), C.sizeof(MapFuseBatch), C.sizeof(RelocParams), C.sizeof(RelocBatch)]
     if list(got) != want:
         _err = HIPLibraryError("struct sizes differ between %s %s and the ctypes layouts %s"
                                % (LIB_PATH, list(got), want))
@@ -335,6 +355,14 @@ def mapmatch_params(**kw):
 def mapfuse_params(**kw):
     p = MapFuseParams()
     load().lslam_mapfuse_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def reloc_params(**kw):
+    p = RelocParams()
+    load().lslam_reloc_params_default(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -7,7 +7,8 @@
 //   stream parser), lslam_ransac.h (fits, residuals), lslam_ukf.h, lslam_express.h (the
 //   express-packet kernels), lslam_match.h (the scan matcher's two kernels), lslam_grid.h
 //   (the occupancy-grid kernel; its integer ray is lslam_grid_ray.h, plain C++), lslam_mapmatch.h
-//   (the scan-to-map matcher's two kernels), lslam_mapfuse.h (the match-fusion kernel);
+//   (the scan-to-map matcher's two kernels), lslam_mapfuse.h (the match-fusion kernel),
+//   lslam_reloc.h (the relocalisation kernels);
 // the host side is included at the foot:
 //   lslam_hazards.h  which waits a call's producer needs (plain C++, no HIP)
 //   lslam_ctx.h      lslam_ctx, its grow-only device buffers and timers, create / destroy,
@@ -3052,6 +3053,8 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
 #include "lslam_mapmatch.h"
 // the match-fusion kernel, after those (it launches mapmatch_search_kernel as it stands)
 #include "lslam_mapfuse.h"
+// the relocalisation kernels, after those (the fine stage is the scan-to-map matcher's as it stands)
+#include "lslam_reloc.h"
 
 // ------------------------------------------------------------------------
 // host side: the context, then the launchers and entry points

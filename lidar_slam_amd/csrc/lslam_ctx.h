@@ -11,6 +11,15 @@ static thread_local std::string g_err;
 
 static size_t default_steps_budget() { return (size_t)2 << 30; }  // lslam_set_steps_budget
 
+// lslam_set_reloc_budget: the score volume of a 4096-robot map match at its defaults, or the environment's
+static size_t default_reloc_budget() {
+    if (const char *e = getenv("LSLAM_RELOC_BUDGET")) {
+        const long long v = atoll(e);
+        if (v > 0) return (size_t)v;
+    }
+    return (size_t)4096 * 41 * 21 * 21 * 4;
+}
+
 static int set_err(int code, const char *msg) {
     g_err = msg;
     return code;
@@ -64,6 +73,8 @@ struct lslam_ctx {
     DevBuf escr;  // express-scan revolution builder scratch (per-packet flags/ranks, per-revolution info)
     DevBuf cscr;  // large-chunk consensus scratch: per-trial counts (+ Philox draws)
     DevBuf mscr;  // score volume of a scan-match or scan-to-map call (when the caller gives no scores)
+    DevBuf rscr;  // relocalisation: a chunk's coarse volume (when the caller gives no coarse_scores) and peak keys
+    size_t reloc_budget = default_reloc_budget();  // bytes of coarse volume per chunk (lslam_set_reloc_budget)
     int resolve_beside = 0;  // this call's resolves will likely run beside the next call's producer
     int n_cus = 1;           // compute units of the device
     uint32_t timing_mask = 0xffffffffu;  // kernel ids timed when timing is on (lslam_set_timing_mask)
@@ -243,7 +254,7 @@ int lslam_ctx_destroy(lslam_ctx *c) {
             if (c->ev0[k][r]) (void)hipEventDestroy(c->ev0[k][r]);
             if (c->ev1[k][r]) (void)hipEventDestroy(c->ev1[k][r]);
         }
-    for (DevBuf *b : {&c->scr, &c->escr, &c->cscr, &c->mscr}) (void)b->release();
+    for (DevBuf *b : {&c->scr, &c->escr, &c->cscr, &c->mscr, &c->rscr}) (void)b->release();
     for (DevBuf &b : c->seedst) (void)b.release();
     for (DevBuf &b : c->cutb) (void)b.release();
     for (DevBuf &b : c->pslot) (void)b.release();
@@ -376,6 +387,12 @@ int lslam_mapmatch_abi_sizes(int64_t *sizes, int n) {
 
 int lslam_mapfuse_abi_sizes(int64_t *sizes, int n) {
     const int64_t s[2] = {(int64_t)sizeof(lslam_mapfuse_params), (int64_t)sizeof(lslam_mapfuse_batch)};
+    for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
+    return 2;
+}
+
+int lslam_reloc_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[2] = {(int64_t)sizeof(lslam_reloc_params), (int64_t)sizeof(lslam_reloc_batch)};
     for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
     return 2;
 }
@@ -528,6 +545,21 @@ int lslam_mapfuse_params_default(lslam_mapfuse_params *p) {
     p->r_scale = 1.0;
     p->nis_max = 16.27;      // the 99.9 % point of chi-square with 3 degrees of freedom
     p->cut_permille = 900;   // the candidates within a tenth of the winner's score
+    return LSLAM_OK;
+}
+
+int lslam_reloc_params_default(lslam_reloc_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->head_step = 2.0 * LS_PI / 180.0;  // two degrees: the fine window's +-10 covers it five times
+    p->n_head = 180;                     // the whole turn
+    p->factor = 4;                       // 80 mm coarse cells at 20 mm: the fine window's +-200 mm covers them
+    p->n_cand = 8;
+    p->ambig_permille = 900;
+    p->dup_mm = 100.0;                   // half the fine translation window
+    p->dup_rad = 0.0873;                 // five degrees
+    p->reset_sigma_xy = 50.0;            // mm
+    p->reset_sigma_theta = 0.05;         // rad
     return LSLAM_OK;
 }
 

@@ -1034,6 +1034,150 @@ static int launch_mapfuse(lslam_ctx *c, const lslam_mapfuse_batch *b, const lsla
     return LSLAM_OK;
 }
 
+// ---- relocalisation (lslam_reloc.h) ----
+
+static int reloc_check_params(const lslam_reloc_params *q, const lslam_grid_params *g, const lslam_mapmatch_params *m) {
+    if (!q) return set_err(LSLAM_ERR_ARG, "reloc: params is NULL");
+    if (!(q->head_step > 0) || !std::isfinite(q->head_step))
+        return set_err(LSLAM_ERR_ARG, "reloc: head_step must be > 0");
+    if (q->n_head < 4 || q->n_head > 1024) return set_err(LSLAM_ERR_ARG, "reloc: n_head must be in [4, 1024]");
+    if (q->factor != 2 && q->factor != 4 && q->factor != 8)
+        return set_err(LSLAM_ERR_ARG, "reloc: factor must be 2, 4 or 8");
+    if (g->grid_w % q->factor != 0 || g->grid_w / q->factor < 4 || g->grid_w / q->factor > 256)
+        return set_err(LSLAM_ERR_ARG, "reloc: factor must divide grid_w, with grid_w / factor in [4, 256]");
+    if (q->n_cand < 1 || q->n_cand > RELOC_KMAX) return set_err(LSLAM_ERR_ARG, "reloc: n_cand must be in [1, 16]");
+    if (q->ambig_permille < 0 || q->ambig_permille > 1000)
+        return set_err(LSLAM_ERR_ARG, "reloc: ambig_permille must be in [0, 1000]");
+    if (!(q->dup_mm >= 0)) return set_err(LSLAM_ERR_ARG, "reloc: dup_mm must be >= 0");
+    if (!(q->dup_rad >= 0)) return set_err(LSLAM_ERR_ARG, "reloc: dup_rad must be >= 0");
+    if (!(q->reset_sigma_xy > 0) || !std::isfinite(q->reset_sigma_xy))
+        return set_err(LSLAM_ERR_ARG, "reloc: reset_sigma_xy must be > 0 and finite");
+    if (!(q->reset_sigma_theta > 0) || !std::isfinite(q->reset_sigma_theta))
+        return set_err(LSLAM_ERR_ARG, "reloc: reset_sigma_theta must be > 0 and finite");
+    if (2 * m->k_trans < q->factor)
+        return set_err(LSLAM_ERR_ARG, "reloc: the fine window must cover a coarse cell: 2 k_trans >= factor");
+    if (!(2.0 * (double)m->k_theta * m->theta_step >= q->head_step))
+        return set_err(LSLAM_ERR_ARG, "reloc: the fine window must cover a heading step: 2 k_theta theta_step >= head_step");
+    return LSLAM_OK;
+}
+
+template <int FORM>
+static int launch_reloc_search(lslam_ctx *c, const RelocArgs &k, int nr) {
+    static std::once_flag once;
+    std::call_once(once, [] { set_max_lds(reloc_search_kernel<FORM>); });
+    hipLaunchKernelGGL(reloc_search_kernel<FORM>, dim3((unsigned)(nr * k.n_slices)), dim3(RELOC_TPB),
+                       reloc_lds_bytes(k.Wc, k.RW), c->stream, k);
+    HIPCHK(hipGetLastError());
+    return LSLAM_OK;
+}
+
+// The coarse stage in chunks of robots under the context's byte budget (search, peaks, the K best),
+// then K times the scan-to-map matcher as launch_mapmatch launches it, rank j's arrays in the place of
+// the batch's, then the selection.  LSLAM_RELOC_FORM=add (tools/relocbench.py) selects the search
+// form that was measured and dropped.
+static int launch_reloc(lslam_ctx *c, const lslam_reloc_batch *b, const lslam_grid_params *g,
+                        const lslam_mapmatch_params *m, const lslam_reloc_params *q) {
+    const int R = b->n_robots, K = q->n_cand;
+    RelocArgs k;
+    memset(&k, 0, sizeof(k));
+    k.b = *b;
+    k.f = q->factor;
+    k.Wc = g->grid_w / q->factor;
+    k.cellc = g->cell * (double)q->factor;
+    k.invc = 1.0 / k.cellc;
+    k.head_step = q->head_step;
+    k.max_r2 = g->max_range * g->max_range;
+    k.dup_mm = q->dup_mm;
+    k.dup_rad = q->dup_rad;
+    k.pxy = q->reset_sigma_xy * q->reset_sigma_xy;
+    k.pth = q->reset_sigma_theta * q->reset_sigma_theta;
+    k.map_w = g->grid_w;
+    k.n_head = q->n_head;
+    k.K = K;
+    k.occ_min = m->occ_min;
+    k.ambig = q->ambig_permille;
+    k.nspan = (k.Wc + 31) / 32;
+    k.RW = reloc_row_dwords(k.Wc, k.nspan);
+    k.vec = (g->grid_w % 8 == 0 && ((uintptr_t)b->logodds & 15) == 0) ? 1 : 0;
+    if (const char *e = getenv("LSLAM_RELOC_FORM"))
+        if (!strcmp(e, "add")) k.form = 1;
+    const size_t cells = (size_t)k.n_head * k.Wc * k.Wc;
+    k.nbh = (k.Wc * k.Wc + RELOC_PEAK_BLOCK - 1) / RELOC_PEAK_BLOCK;
+    k.nblk = k.n_head * k.nbh;
+    const int nc = (int)std::min<size_t>((size_t)R, std::max<size_t>(1, c->reloc_budget / (cells * 4)));
+    const int64_t want = 2 * (int64_t)c->n_cus;
+    int64_t ns = (want + nc - 1) / nc;
+    ns = std::min<int64_t>(std::max<int64_t>(ns, 1), k.n_head);
+    k.per_slice = (int)((k.n_head + ns - 1) / ns);
+    k.n_slices = (k.n_head + k.per_slice - 1) / k.per_slice;
+    if ((int64_t)nc * k.nblk >= ((int64_t)1 << 31)) return set_err(LSLAM_ERR_UNSUPPORTED, "reloc: too many robots in one call");
+    const size_t keys_bytes = ((size_t)nc * k.nblk * K * 8 + 255) & ~(size_t)255;
+    int st = c->rscr.ensure(c, keys_bytes + (b->coarse_scores ? 0 : (size_t)nc * cells * 4), "reloc scratch");
+    if (st) return st;
+    k.keys = c->rscr.as<unsigned long long>();
+    // the fine stage's batch of rank 0: its scratch is grown here, before the timer and the first launch
+    lslam_mapmatch_batch mb;
+    memset(&mb, 0, sizeof(mb));
+    mb.n_robots = R;
+    mb.xy = b->xy;
+    mb.pt_off = b->pt_off;
+    mb.origin = b->origin;
+    mb.logodds = b->logodds;
+    mb.rot = b->rot;
+    MapMatchArgs mk;
+    size_t mvol;
+    if ((st = mapmatch_args(c, &mb, g, m, mk, mvol))) return st;
+    if ((st = timer_begin(c, LSLAM_K_RELOC))) return st;
+    for (int r0 = 0; r0 < R; r0 += nc) {
+        const int nr = std::min(nc, R - r0);
+        k.r0 = r0;
+        k.vol = b->coarse_scores ? b->coarse_scores + (size_t)r0 * cells : (int32_t *)(c->rscr.as<char>() + keys_bytes);
+        if ((st = k.form ? launch_reloc_search<1>(c, k, nr) : launch_reloc_search<0>(c, k, nr))) return st;
+        hipLaunchKernelGGL(reloc_peak_kernel, dim3((unsigned)(nr * k.nblk)), dim3(RELOC_PEAK_TPB), 0, c->stream, k);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(reloc_topk_kernel, dim3((unsigned)nr), dim3(RELOC_PEAK_TPB), 0, c->stream, k);
+        HIPCHK(hipGetLastError());
+    }
+    const size_t Rz = (size_t)R;
+    // LSLAM_RELOC_STAGES=coarse (tools/relocbench.py): the coarse stage alone; the fine outputs, result, flags
+    // and pose_out are not written
+    const char *stages = getenv("LSLAM_RELOC_STAGES");
+    if (stages && !strcmp(stages, "coarse")) return timer_end(c, LSLAM_K_RELOC);
+    for (int j = 0; j < K; j++) {
+        mb.pose = b->cand_pose + (size_t)j * Rz * 3;
+        mb.pose_out = b->fine_pose + (size_t)j * Rz * 3;
+        mb.delta = b->fine_delta + (size_t)j * Rz * 3;
+        mb.best = b->fine_best + (size_t)j * Rz * 4;
+        mb.n_valid = b->fine_nvalid + (size_t)j * Rz * 2;
+        mb.rot0 = b->fine_rot0 + (size_t)j * Rz * 2;
+        mb.flags = b->fine_flags + (size_t)j * Rz;
+        if ((st = mapmatch_args(c, &mb, g, m, mk, mvol))) return st;  // (the stream orders the reuse of its scratch)
+        if ((st = launch_mapmatch_search(c, mk))) return st;
+        hipLaunchKernelGGL(mapmatch_pick_kernel, dim3((unsigned)R), dim3(MATCH_PICK_TPB), 0, c->stream, mk);
+        HIPCHK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(reloc_select_kernel, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, c->stream, k);
+    HIPCHK(hipGetLastError());
+    if ((st = timer_end(c, LSLAM_K_RELOC))) return st;
+    const size_t KR = (size_t)K * Rz;
+    c->hz.outs.add(b->n_occ, Rz * 4);
+    c->hz.outs.add(b->n_used, Rz * 4);
+    c->hz.outs.add(b->cand, KR * 16);
+    c->hz.outs.add(b->cand_pose, KR * 24);
+    c->hz.outs.add(b->fine_pose, KR * 24);
+    c->hz.outs.add(b->fine_delta, KR * 24);
+    c->hz.outs.add(b->fine_best, KR * 16);
+    c->hz.outs.add(b->fine_nvalid, KR * 8);
+    c->hz.outs.add(b->fine_rot0, KR * 16);
+    c->hz.outs.add(b->fine_flags, KR * 4);
+    c->hz.outs.add(b->result, Rz * 32);
+    c->hz.outs.add(b->flags, Rz * 4);
+    c->hz.outs.add(b->pose_out, Rz * 24);
+    c->hz.outs.add(b->P_out, Rz * 72);
+    c->hz.outs.add(b->coarse_scores, Rz * cells * 4);
+    return LSLAM_OK;
+}
+
 // ---- express-scan codec (lslam_express.h) ----
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1273,6 +1417,37 @@ int lslam_map_fuse(lslam_ctx *c, const lslam_mapfuse_batch *b, const lslam_grid_
     if (b->m.n_robots == 0) return LSLAM_OK;
     HIPCHK(hipSetDevice(c->device));
     return launch_mapfuse(c, b, g, m, f);
+}
+
+// On the main stream, as lslam_map_match.
+int lslam_map_relocalize(lslam_ctx *c, const lslam_reloc_batch *b, const lslam_grid_params *g,
+                         const lslam_mapmatch_params *m, const lslam_reloc_params *q) {
+    int st = mapmatch_check_params(m);
+    if (st) return st;
+    if ((st = grid_check_params(g))) return st;
+    if ((st = reloc_check_params(q, g, m))) return st;
+    if (!b) return set_err(LSLAM_ERR_ARG, "reloc: batch is NULL");
+    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "reloc: negative n_robots");
+    if (b->n_robots > 0) {
+        if (!b->xy || !b->pt_off || !b->origin || !b->logodds || !b->rot || !b->head_rot)
+            return set_err(LSLAM_ERR_ARG, "reloc: missing input (xy, pt_off, origin, logodds, rot, head_rot)");
+        if (!b->n_occ || !b->n_used || !b->cand || !b->cand_pose || !b->fine_pose || !b->fine_delta || !b->fine_best ||
+            !b->fine_nvalid || !b->fine_rot0 || !b->fine_flags || !b->result || !b->flags || !b->pose_out)
+            return set_err(LSLAM_ERR_ARG,
+                           "reloc: missing output (n_occ, n_used, cand, cand_pose, fine_pose, fine_delta, fine_best, "
+                           "fine_nvalid, fine_rot0, fine_flags, result, flags, pose_out)");
+    }
+    if (!c) return set_err(LSLAM_ERR_ARG, "reloc: ctx is NULL");
+    if (b->n_robots == 0) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return launch_reloc(c, b, g, m, q);
+}
+
+// (the scratch is sized per call: a call in flight keeps the chunking it was launched with)
+int lslam_set_reloc_budget(lslam_ctx *c, int64_t bytes) {
+    if (!c) return LSLAM_ERR_ARG;
+    c->reloc_budget = bytes > 0 ? (size_t)bytes : default_reloc_budget();
+    return LSLAM_OK;
 }
 
 int lslam_express_decode(lslam_ctx *c, const uint8_t *packets, int64_t n_packets, const lslam_express_measures *out) {

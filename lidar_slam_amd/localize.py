@@ -24,9 +24,21 @@ never leave HBM::
 The grid was drawn from the filter's own poses, so the match is not independent of the prior;
 ``r_scale`` (a factor on the match covariance) is the knob for that.
 
-The definitions are the comments on ``lslam_map_match`` and ``lslam_map_fuse`` in
-include/lidarslam.h; tests/mapmatch_ref.py and tests/mapfuse_ref.py are their NumPy forms and the
-kernels match them bit for bit, given the (cos, sin) that the library wrote to ``rot0``.
+``GridRelocalizer`` (``lslam_map_relocalize``) finds the pose that a guess cannot reach: the start in
+a stored grid, the kidnapped robot.  It needs no guess.  A coarse correlative search over every
+coarse cell of the grid and every heading gives the K best separated peaks, ``lslam_map_match``
+refines each, and the best refined pose is returned unless a second, distinct one scores nearly as
+well (``RELOC_AMBIGUOUS``: a room that looks the same after a half turn) or none passes the fine
+matcher's gates (``RELOC_LOST``).  With ``lm`` a found robot's mean and covariance are re-seated in
+the filter on the device; the others keep theirs::
+
+    grid.upload(stored)                                        # a restart
+    rel.relocalize(xy, scan_chunk_off, chunk_pt_off, grid=grid, lm=lm)
+
+The definitions are the comments on ``lslam_map_match``, ``lslam_map_fuse`` and
+``lslam_map_relocalize`` in include/lidarslam.h; tests/mapmatch_ref.py, tests/mapfuse_ref.py and
+tests/reloc_ref.py are their NumPy forms and the kernels match them bit for bit, given the
+(cos, sin) that the library wrote to ``rot0``.
 """
 from __future__ import annotations
 
@@ -44,7 +56,18 @@ MAPMATCH_EMPTY, MAPMATCH_EDGE = _lib.MAPMATCH_EMPTY, _lib.MAPMATCH_EDGE
 MAPMATCH_BAD_POSE, MAPMATCH_WEAK = _lib.MAPMATCH_BAD_POSE, _lib.MAPMATCH_WEAK
 MAPFUSE_OUTLIER, MAPFUSE_BAD_COV = _lib.MAPFUSE_OUTLIER, _lib.MAPFUSE_BAD_COV
 
+RELOC_LOST, RELOC_AMBIGUOUS = _lib.RELOC_LOST, _lib.RELOC_AMBIGUOUS
+
 _FUSE_KEYS = ("r_scale", "nis_max", "cut_permille")
+_RELOC_KEYS = ("head_step", "n_head", "factor", "n_cand", "ambig_permille", "dup_mm", "dup_rad", "reset_sigma_xy",
+               "reset_sigma_theta")
+
+
+def head_table(n_head, head_step):
+    """(cos, sin) of k * head_step, [n_head, 2] float64: the coarse search's headings.  As with
+    ``rot_table`` the library never computes these itself: the caller's bits are the definition."""
+    a = np.arange(int(n_head)).astype(np.float64) * float(head_step)
+    return np.ascontiguousarray(np.stack([np.cos(a), np.sin(a)], -1))
 
 
 class GridLocalizer:
@@ -229,4 +252,106 @@ class GridLocalizer:
             out["z"], out["nis"] = self._fused["z"].download(), self._fused["nis"].download()
             out["Rm"] = self._fused["Rm"].download().reshape(-1, 3, 3)
             out["moments"] = self._fused["moments"].download()
+        return out
+
+
+class GridRelocalizer:
+    """R robots per call on one GPU.  ``params``: head_step, n_head, factor, n_cand, ambig_permille,
+    dup_mm, dup_rad, reset_sigma_xy, reset_sigma_theta (``lslam_reloc_params``; defaults 2 pi / 180,
+    180, 4, 8, 900, 100.0, 0.0873, 50.0, 0.05) and the fine matcher's (``lslam_mapmatch_params``, as
+    ``GridLocalizer``).  The cell size, the map's width and max_range are the grid's, given with each
+    call."""
+
+    _PER_RANK = (("cand", 4, np.int32), ("cand_pose", 3, np.float64), ("fine_pose", 3, np.float64),
+                 ("fine_delta", 3, np.float64), ("fine_best", 4, np.int32), ("fine_nvalid", 2, np.int32),
+                 ("fine_rot0", 2, np.float64), ("fine_flags", 1, np.int32))
+
+    def __init__(self, ctx: Context, n_robots: int, **params):
+        R = int(n_robots)
+        if R <= 0:
+            raise ValueError("n_robots must be > 0")
+        self.ctx, self.R = ctx, R
+        self.q = _lib.reloc_params(**{k: params.pop(k) for k in _RELOC_KEYS if k in params})
+        self.p = _lib.mapmatch_params(**params)
+        # (a range error of params surfaces here, from the first call)
+        _lib.check(_lib.load().lslam_map_relocalize(ctx.handle, C.byref(_lib.RelocBatch()), C.byref(_lib.grid_params()),
+                                                    C.byref(self.p), C.byref(self.q)), "lslam_map_relocalize")
+        K = self.K = int(self.q.n_cand)
+        self.rot_host = rot_table(self.p.k_theta, self.p.theta_step)
+        self.rot = ctx.to_device(self.rot_host)
+        self.head_rot_host = head_table(self.q.n_head, self.q.head_step)
+        self.head_rot = ctx.to_device(self.head_rot_host)
+        self.pose = ctx.empty((R, 3), np.float64)  # pose_out, unless a call re-seats a filter
+        self.n_occ, self.n_used = ctx.empty(R, np.int32), ctx.empty(R, np.int32)
+        self.result, self.flags = ctx.empty((R, 8), np.int32), ctx.empty(R, np.int32)
+        self.ranks = {n: ctx.empty((K, R, w) if w > 1 else (K, R), dt) for n, w, dt in self._PER_RANK}
+        for a in (self.n_occ, self.n_used, self.result, self.flags) + tuple(self.ranks.values()):
+            a.fill_zero()
+        self.coarse = None
+        self._xy = _Grow(ctx, np.float64)
+        self._off = ctx.empty(R + 1, np.int32)
+        self._have_coarse = False
+        self._out, self._P_out = self.pose, None
+        self.calls = 0
+
+    def set_budget(self, nbytes):
+        """Bytes of coarse-score scratch per chunk of robots (``lslam_set_reloc_budget``; <= 0: the
+        default).  No result depends on it."""
+        _lib.check(_lib.load().lslam_set_reloc_budget(self.ctx.handle, int(nbytes)), "lslam_set_reloc_budget")
+
+    def relocalize(self, xy, scan_chunk_off=None, chunk_pt_off=None, grid=None, lm=None, want_coarse=False, sync=True):
+        """One revolution per robot, in the forms ``GridLocalizer.step`` accepts; ``grid``: the
+        ``OccupancyGrid`` to find the robots in.  With ``lm`` (a ``LandmarkMap``) the pose of a found,
+        unambiguous robot is written over ``lm.x`` and diag(reset_sigma_xy^2, reset_sigma_xy^2,
+        reset_sigma_theta^2) over its ``lm.P``; LOST and AMBIGUOUS robots keep the bits of both.
+        Without it the poses go to ``self.pose``, NaN where none was found."""
+        ctx, R, K = self.ctx, self.R, self.K
+        if lm is not None:
+            if not isinstance(lm, LandmarkMap):
+                raise ValueError("lm must be a LandmarkMap")
+            if lm.R != R:
+                raise ValueError("the map holds %d robots, the localizer %d" % (lm.R, R))
+        dxy, off = GridLocalizer._revolutions(self, xy, scan_chunk_off, chunk_pt_off, grid)
+        self._off.upload_async(np.ascontiguousarray(off, np.int32))
+        b = _lib.RelocBatch()
+        b.n_robots = R
+        b.xy, b.pt_off, b.origin, b.logodds = dxy.addr, self._off.addr, grid.origin.addr, grid.logodds.addr
+        b.rot, b.head_rot = self.rot.addr, self.head_rot.addr
+        b.n_occ, b.n_used, b.result, b.flags = self.n_occ.addr, self.n_used.addr, self.result.addr, self.flags.addr
+        for n, _, _ in self._PER_RANK:
+            setattr(b, n, self.ranks[n].addr)
+        if lm is not None:
+            self._out, self._P_out = lm.x, lm.P
+            b.P_out = lm.P.addr
+        else:
+            self._out, self._P_out = self.pose, None
+            self.pose.upload_async(np.full((R, 3), np.nan))
+        b.pose_out = self._out.addr
+        if want_coarse:
+            Wc = grid.W // int(self.q.factor)
+            shape = (R, int(self.q.n_head), Wc, Wc)
+            if self.coarse is None or self.coarse.shape != shape:
+                self.coarse = ctx.empty(shape, np.int32)
+            b.coarse_scores = self.coarse.addr
+        self._have_coarse = bool(want_coarse)
+        _lib.check(_lib.load().lslam_map_relocalize(ctx.handle, C.byref(b), C.byref(grid.p), C.byref(self.p),
+                                                    C.byref(self.q)), "lslam_map_relocalize")
+        self.calls += 1
+        if sync:
+            ctx.sync()
+
+    def results(self):
+        """The last call's pose [R, 3] (``lm.x`` after a call with ``lm``), flags [R] (RELOC_*),
+        result [R, 8] (winner rank, its k, ty, tx, coarse score, fine score, best rival's rank or -1,
+        its fine score), n_occ [R], n_used [R], per rank j < K cand [K, R, 4], cand_pose [K, R, 3] and
+        the fine matcher's fine_pose, fine_delta, fine_best, fine_nvalid, fine_rot0, fine_flags
+        [K, R, ..]; P [R, 3, 3] after a call with ``lm``; coarse_scores [R, n_head, Wc, Wc] when asked for."""
+        out = {"pose": self._out.download().reshape(-1, 3)[:self.R], "flags": self.flags.download(),
+               "result": self.result.download(), "n_occ": self.n_occ.download(), "n_used": self.n_used.download()}
+        for n, _, _ in self._PER_RANK:
+            out[n] = self.ranks[n].download()
+        if self._P_out is not None:
+            out["P"] = self._P_out.download().reshape(-1, 3, 3)[:self.R]
+        if self._have_coarse:
+            out["coarse_scores"] = self.coarse.download()
         return out
