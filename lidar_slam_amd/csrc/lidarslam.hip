@@ -5,7 +5,8 @@
 // One translation unit.  This file holds the kernels; their device code is in
 //   lslam_wave.h (wave primitives), lslam_rng.h / lslam_rng_pipe.h (MT19937, Philox, the
 //   stream parser), lslam_ransac.h (fits, residuals), lslam_ukf.h, lslam_express.h (the
-//   express-packet kernels), lslam_match.h (the scan matcher's two kernels), lslam_grid.h
+//   express-packet kernels), lslam_corr.h (the correlative search that both matchers share),
+//   lslam_match.h (the scan matcher's two kernels), lslam_grid.h
 //   (the occupancy-grid kernel; its integer ray is lslam_grid_ray.h, plain C++), lslam_mapmatch.h
 //   (the scan-to-map matcher's two kernels), lslam_mapfuse.h (the match-fusion kernel),
 //   lslam_reloc.h (the relocalisation kernels);
@@ -3046,14 +3047,15 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
 
 
 // the scan matcher's kernels: after every other kernel, whose places in the code object they leave alone
+// (it brings in lslam_corr.h, the correlative-search core that both matchers are built on)
 #include "lslam_match.h"
 // the occupancy-grid kernel, after those
 #include "lslam_grid.h"
-// the scan-to-map matcher's two kernels, last (they share lslam_match.h's device functions)
+// the scan-to-map matcher's two kernels, after that: lslam_corr.h's search over a window of the grid
 #include "lslam_mapmatch.h"
-// the match-fusion kernel, after those (it launches mapmatch_search_kernel as it stands)
+// the match-fusion kernel, after those: the scan-to-map search, then a pick kernel of its own
 #include "lslam_mapfuse.h"
-// the relocalisation kernels, after those (the fine stage is the scan-to-map matcher's as it stands)
+// the relocalisation kernels, after those: a coarse search of their own around the scan-to-map matcher
 #include "lslam_reloc.h"
 
 // ------------------------------------------------------------------------

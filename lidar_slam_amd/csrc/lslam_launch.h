@@ -751,70 +751,87 @@ static int run_split(lslam_ctx *c, const lslam_scan_batch *b, const lslam_ransac
 }
 
 
+// ---- the correlative search (lslam_corr.h): what the scan matcher and the scan-to-map matcher share ----
+
+// The range checks of both matchers' params; who: the errors' prefix, width_name: the width field's name.
+static int corr_check_params(const char *who, const char *width_name, double theta_step, int width, int smear, int k_trans,
+                             int k_theta) {
+    const std::string p = std::string(who) + ": ";
+    if (!(theta_step > 0) || !std::isfinite(theta_step)) return set_err(LSLAM_ERR_ARG, (p + "theta_step must be > 0").c_str());
+    if (width < 16 || width > 512 || (width & 1))
+        return set_err(LSLAM_ERR_ARG, (p + width_name + " must be even, in [16, 512]").c_str());
+    if (smear < 0 || smear > 2) return set_err(LSLAM_ERR_ARG, (p + "smear must be in [0, 2]").c_str());
+    if (k_trans < 0 || k_trans > 15) return set_err(LSLAM_ERR_ARG, (p + "k_trans must be in [0, 15]").c_str());
+    if (k_theta < 0 || k_theta > 31) return set_err(LSLAM_ERR_ARG, (p + "k_theta must be in [0, 31]").c_str());
+    return LSLAM_OK;
+}
+
+// The geometry of a search over n robots, the slice rule and the score volume (the caller's `scores`
+// or the context's scratch; vol = its bytes).  Slices: enough for two workgroups per CU (what the
+// LDS allows) when the robots alone do not give them, at most one per rotation; each slice rebuilds G.
+static int corr_geometry(lslam_ctx *c, const char *who, int n, double cell, double theta_step, int width, int smear,
+                         int k_trans, int k_theta, int32_t *scores, CorrGeom &g, size_t &vol) {
+    g.cell = cell;
+    g.inv = 1.0 / cell;
+    g.theta_step = theta_step;
+    g.n = n;
+    g.win_w = width;
+    g.half = width / 2;
+    g.smear = smear;
+    g.kt = k_trans;
+    g.kth = k_theta;
+    g.Nt = 2 * k_trans + 1;
+    g.Nth = 2 * k_theta + 1;
+    g.W = width + 2 * k_trans;
+    g.Sd = match_row_dwords(g.W);
+    const int64_t want = 2 * (int64_t)c->n_cus;
+    int64_t ns = (want + n - 1) / n;
+    ns = std::min<int64_t>(std::max<int64_t>(ns, 1), g.Nth);
+    g.per_slice = (int)((g.Nth + ns - 1) / ns);
+    g.n_slices = (g.Nth + g.per_slice - 1) / g.per_slice;
+    if ((int64_t)n * g.n_slices >= ((int64_t)1 << 31))
+        return set_err(LSLAM_ERR_UNSUPPORTED, (std::string(who) + ": too many robots in one call").c_str());
+    vol = (size_t)n * g.Nth * g.Nt * g.Nt * 4;
+    g.scores = scores;
+    if (!scores) {
+        int st = c->mscr.ensure(c, vol, (std::string(who) + " scores").c_str());
+        if (st) return st;
+        g.scores = c->mscr.as<int32_t>();
+    }
+    return LSLAM_OK;
+}
+
 // ---- scan matcher (lslam_match.h) ----
 
 static int match_check_params(const lslam_match_params *p) {
     if (!p) return set_err(LSLAM_ERR_ARG, "match: params is NULL");
     if (!(p->cell > 0) || !std::isfinite(p->cell)) return set_err(LSLAM_ERR_ARG, "match: cell must be > 0");
-    if (!(p->theta_step > 0) || !std::isfinite(p->theta_step))
-        return set_err(LSLAM_ERR_ARG, "match: theta_step must be > 0");
-    if (p->grid_w < 16 || p->grid_w > 512 || (p->grid_w & 1))
-        return set_err(LSLAM_ERR_ARG, "match: grid_w must be even, in [16, 512]");
-    if (p->smear < 0 || p->smear > 2) return set_err(LSLAM_ERR_ARG, "match: smear must be in [0, 2]");
-    if (p->k_trans < 0 || p->k_trans > 15) return set_err(LSLAM_ERR_ARG, "match: k_trans must be in [0, 15]");
-    if (p->k_theta < 0 || p->k_theta > 31) return set_err(LSLAM_ERR_ARG, "match: k_theta must be in [0, 31]");
-    return LSLAM_OK;
+    return corr_check_params("match", "grid_w", p->theta_step, p->grid_w, p->smear, p->k_trans, p->k_theta);
 }
 
 // match_search_kernel on a grid of (robots x rotation slices), then match_pick_kernel per robot.
-// Slices: enough for two workgroups per CU (what the LDS allows) when the robots alone do not
-// give them, at most one per rotation; each slice rebuilds G.
 static int launch_match(lslam_ctx *c, const lslam_match_batch *b, const lslam_match_params *p,
                         const lslam_ukf_params *u) {
     MatchArgs k;
     memset(&k, 0, sizeof(k));
     k.b = *b;
-    k.cell = p->cell;
-    k.inv = 1.0 / p->cell;
-    k.theta_step = p->theta_step;
-    k.grid_w = p->grid_w;
-    k.half = p->grid_w / 2;
-    k.smear = p->smear;
-    k.kt = p->k_trans;
-    k.kth = p->k_theta;
-    k.Nt = 2 * p->k_trans + 1;
-    k.Nth = 2 * p->k_theta + 1;
-    k.W = p->grid_w + 2 * p->k_trans;
-    k.Sd = match_row_dwords(k.W);
+    size_t vol;
+    int st = corr_geometry(c, "match", b->n_scans, p->cell, p->theta_step, p->grid_w, p->smear, p->k_trans, p->k_theta,
+                           b->scores, k.g, vol);
+    if (st) return st;
     k.write_u = (u && b->ukf_u) ? 1 : 0;
     if (k.write_u) {
         k.dt = u->dt;
         k.wr = u->wheel_radius;
         k.wb = u->wheel_base;
     }
-    const int64_t want = 2 * (int64_t)c->n_cus;
-    int64_t ns = (want + b->n_scans - 1) / b->n_scans;
-    ns = std::min<int64_t>(std::max<int64_t>(ns, 1), k.Nth);
-    k.per_slice = (int)((k.Nth + ns - 1) / ns);
-    k.n_slices = (k.Nth + k.per_slice - 1) / k.per_slice;
-    if ((int64_t)b->n_scans * k.n_slices >= ((int64_t)1 << 31))
-        return set_err(LSLAM_ERR_UNSUPPORTED, "match: too many robots in one call");
-    const size_t vol = (size_t)b->n_scans * k.Nth * k.Nt * k.Nt * 4;
-    if (b->scores) {
-        k.scores = b->scores;
-    } else {
-        int st = c->mscr.ensure(c, vol, "match scores");
-        if (st) return st;
-        k.scores = c->mscr.as<int32_t>();
-    }
-    const int lds = match_lds_bytes(k.W, k.Sd, k.Nt);
+    const int lds = match_lds_bytes(k.g.W, k.g.Sd, k.g.Nt);
     static std::once_flag once;
     std::call_once(once, [] { set_max_lds(match_search_kernel); });
-    int st = timer_begin(c, LSLAM_K_MATCH);
-    if (st) return st;
-    hipLaunchKernelGGL(match_search_kernel, dim3((unsigned)(b->n_scans * k.n_slices)), dim3(MATCH_TPB), lds, c->stream, k);
+    if ((st = timer_begin(c, LSLAM_K_MATCH))) return st;
+    hipLaunchKernelGGL(match_search_kernel, dim3((unsigned)(k.g.n * k.g.n_slices)), dim3(MATCH_TPB), lds, c->stream, k);
     HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(match_pick_kernel, dim3((unsigned)b->n_scans), dim3(MATCH_PICK_TPB), 0, c->stream, k);
+    hipLaunchKernelGGL(match_pick_kernel, dim3((unsigned)k.g.n), dim3(MATCH_PICK_TPB), 0, c->stream, k);
     HIPCHK(hipGetLastError());
     if ((st = timer_end(c, LSLAM_K_MATCH))) return st;
     const size_t S = (size_t)b->n_scans;
@@ -893,13 +910,8 @@ static int launch_grid(lslam_ctx *c, const lslam_grid_batch *b, const lslam_grid
 
 static int mapmatch_check_params(const lslam_mapmatch_params *m) {
     if (!m) return set_err(LSLAM_ERR_ARG, "mapmatch: params is NULL");
-    if (!(m->theta_step > 0) || !std::isfinite(m->theta_step))
-        return set_err(LSLAM_ERR_ARG, "mapmatch: theta_step must be > 0");
-    if (m->win_w < 16 || m->win_w > 512 || (m->win_w & 1))
-        return set_err(LSLAM_ERR_ARG, "mapmatch: win_w must be even, in [16, 512]");
-    if (m->smear < 0 || m->smear > 2) return set_err(LSLAM_ERR_ARG, "mapmatch: smear must be in [0, 2]");
-    if (m->k_trans < 0 || m->k_trans > 15) return set_err(LSLAM_ERR_ARG, "mapmatch: k_trans must be in [0, 15]");
-    if (m->k_theta < 0 || m->k_theta > 31) return set_err(LSLAM_ERR_ARG, "mapmatch: k_theta must be in [0, 31]");
+    int st = corr_check_params("mapmatch", "win_w", m->theta_step, m->win_w, m->smear, m->k_trans, m->k_theta);
+    if (st) return st;
     if (m->occ_min < -32768 || m->occ_min > 32767)
         return set_err(LSLAM_ERR_ARG, "mapmatch: occ_min must be in [-32768, 32767]");
     if (m->min_permille < 0 || m->min_permille > 1000)
@@ -907,71 +919,52 @@ static int mapmatch_check_params(const lslam_mapmatch_params *m) {
     return LSLAM_OK;
 }
 
-// The kernels' arguments of a scan-to-map search (shared with launch_mapfuse): geometry, the slice
-// rule and the score volume, the caller's or the context's scratch; vol = its bytes.
+// The matcher's pointers of a scan-to-map batch: 0 all there, 1 an input missing, 2 an output missing.
+// (The callers keep their own texts: lslam_map_fuse names more pointers.)
+static int mapmatch_missing(const lslam_mapmatch_batch *b) {
+    if (!b->xy || !b->pt_off || !b->pose || !b->origin || !b->logodds || !b->rot) return 1;
+    if (!b->pose_out || !b->delta || !b->best || !b->n_valid || !b->rot0 || !b->flags) return 2;
+    return 0;
+}
+
+// The kernels' arguments of a scan-to-map search (launch_mapmatch, launch_mapfuse and the fine stage
+// of launch_reloc); vol = the score volume's bytes.
 static int mapmatch_args(lslam_ctx *c, const lslam_mapmatch_batch *b, const lslam_grid_params *g,
                          const lslam_mapmatch_params *m, MapMatchArgs &k, size_t &vol) {
     memset(&k, 0, sizeof(k));
     k.b = *b;
-    k.cell = g->cell;
-    k.inv = 1.0 / g->cell;
-    k.theta_step = m->theta_step;
     k.map_w = g->grid_w;
-    k.win_w = m->win_w;
-    k.half = m->win_w / 2;
-    k.smear = m->smear;
-    k.kt = m->k_trans;
-    k.kth = m->k_theta;
-    k.Nt = 2 * m->k_trans + 1;
-    k.Nth = 2 * m->k_theta + 1;
-    k.W = m->win_w + 2 * m->k_trans;
-    k.Sd = match_row_dwords(k.W);
     k.occ_min = m->occ_min;
     k.min_permille = m->min_permille;
     k.vec = (g->grid_w % 8 == 0 && ((uintptr_t)b->logodds & 15) == 0) ? 1 : 0;
     // LSLAM_MAPMATCH_FORM=cell (tools/mapmatchbench.py): the lane-per-cell window load on every map
     if (const char *e = getenv("LSLAM_MAPMATCH_FORM"))
         if (!strcmp(e, "cell")) k.vec = 0;
-    const int64_t want = 2 * (int64_t)c->n_cus;
-    int64_t ns = (want + b->n_robots - 1) / b->n_robots;
-    ns = std::min<int64_t>(std::max<int64_t>(ns, 1), k.Nth);
-    k.per_slice = (int)((k.Nth + ns - 1) / ns);
-    k.n_slices = (k.Nth + k.per_slice - 1) / k.per_slice;
-    if ((int64_t)b->n_robots * k.n_slices >= ((int64_t)1 << 31))
-        return set_err(LSLAM_ERR_UNSUPPORTED, "mapmatch: too many robots in one call");
-    vol = (size_t)b->n_robots * k.Nth * k.Nt * k.Nt * 4;
-    if (b->scores) {
-        k.scores = b->scores;
-    } else {
-        int st = c->mscr.ensure(c, vol, "mapmatch scores");
-        if (st) return st;
-        k.scores = c->mscr.as<int32_t>();
-    }
-    return LSLAM_OK;
+    return corr_geometry(c, "mapmatch", b->n_robots, g->cell, m->theta_step, m->win_w, m->smear, m->k_trans, m->k_theta,
+                         b->scores, k.g, vol);
 }
 
 static int launch_mapmatch_search(lslam_ctx *c, const MapMatchArgs &k) {
-    const int lds = mapmatch_lds_bytes(k.W, k.Sd, k.Nt);
+    const int lds = mapmatch_lds_bytes(k.g.W, k.g.Sd, k.g.Nt);
     static std::once_flag once;
     std::call_once(once, [] { set_max_lds(mapmatch_search_kernel); });
-    hipLaunchKernelGGL(mapmatch_search_kernel, dim3((unsigned)(k.b.n_robots * k.n_slices)), dim3(MATCH_TPB), lds, c->stream, k);
+    hipLaunchKernelGGL(mapmatch_search_kernel, dim3((unsigned)(k.g.n * k.g.n_slices)), dim3(MATCH_TPB), lds, c->stream, k);
     HIPCHK(hipGetLastError());
     return LSLAM_OK;
 }
 
-// mapmatch_search_kernel on a grid of (robots x rotation slices), then mapmatch_pick_kernel per
-// robot: the slice rule of launch_match (each slice reads the window and rebuilds G).
-static int launch_mapmatch(lslam_ctx *c, const lslam_mapmatch_batch *b, const lslam_grid_params *g,
-                           const lslam_mapmatch_params *m) {
-    MapMatchArgs k;
-    size_t vol;
-    int st = mapmatch_args(c, b, g, m, k, vol);
+// mapmatch_search_kernel on a grid of (robots x rotation slices), each slice reading the window and
+// rebuilding G, then mapmatch_pick_kernel per robot.
+static int launch_mapmatch_kernels(lslam_ctx *c, const MapMatchArgs &k) {
+    int st = launch_mapmatch_search(c, k);
     if (st) return st;
-    if ((st = timer_begin(c, LSLAM_K_MAPMATCH))) return st;
-    if ((st = launch_mapmatch_search(c, k))) return st;
-    hipLaunchKernelGGL(mapmatch_pick_kernel, dim3((unsigned)b->n_robots), dim3(MATCH_PICK_TPB), 0, c->stream, k);
+    hipLaunchKernelGGL(mapmatch_pick_kernel, dim3((unsigned)k.g.n), dim3(MATCH_PICK_TPB), 0, c->stream, k);
     HIPCHK(hipGetLastError());
-    if ((st = timer_end(c, LSLAM_K_MAPMATCH))) return st;
+    return LSLAM_OK;
+}
+
+// the matcher's outputs, for the hazard planner
+static void mapmatch_outs(lslam_ctx *c, const lslam_mapmatch_batch *b, size_t vol) {
     const size_t R = (size_t)b->n_robots;
     c->hz.outs.add(b->pose_out, R * 24);
     c->hz.outs.add(b->delta, R * 24);
@@ -980,6 +973,18 @@ static int launch_mapmatch(lslam_ctx *c, const lslam_mapmatch_batch *b, const ls
     c->hz.outs.add(b->rot0, R * 16);
     c->hz.outs.add(b->flags, R * 4);
     c->hz.outs.add(b->scores, vol);
+}
+
+static int launch_mapmatch(lslam_ctx *c, const lslam_mapmatch_batch *b, const lslam_grid_params *g,
+                           const lslam_mapmatch_params *m) {
+    MapMatchArgs k;
+    size_t vol;
+    int st = mapmatch_args(c, b, g, m, k, vol);
+    if (st) return st;
+    if ((st = timer_begin(c, LSLAM_K_MAPMATCH))) return st;
+    if ((st = launch_mapmatch_kernels(c, k))) return st;
+    if ((st = timer_end(c, LSLAM_K_MAPMATCH))) return st;
+    mapmatch_outs(c, b, vol);
     return LSLAM_OK;
 }
 
@@ -995,8 +1000,7 @@ static int mapfuse_check_params(const lslam_mapfuse_params *f) {
     return LSLAM_OK;
 }
 
-// mapmatch_search_kernel as launch_mapmatch launches it (the same slice rule, the same scratch
-// volume), then mapfuse_pick_kernel per robot.
+// launch_mapmatch with mapfuse_pick_kernel in the place of mapmatch_pick_kernel.
 static int launch_mapfuse(lslam_ctx *c, const lslam_mapfuse_batch *b, const lslam_grid_params *g,
                           const lslam_mapmatch_params *m, const lslam_mapfuse_params *f) {
     MapFuseArgs k;
@@ -1015,17 +1019,11 @@ static int launch_mapfuse(lslam_ctx *c, const lslam_mapfuse_batch *b, const lsla
     k.cut_permille = f->cut_permille;
     if ((st = timer_begin(c, LSLAM_K_MAPFUSE))) return st;
     if ((st = launch_mapmatch_search(c, k.m))) return st;
-    hipLaunchKernelGGL(mapfuse_pick_kernel<0>, dim3((unsigned)b->m.n_robots), dim3(MATCH_PICK_TPB), 0, c->stream, k);
+    hipLaunchKernelGGL(mapfuse_pick_kernel<0>, dim3((unsigned)k.m.g.n), dim3(MATCH_PICK_TPB), 0, c->stream, k);
     HIPCHK(hipGetLastError());
     if ((st = timer_end(c, LSLAM_K_MAPFUSE))) return st;
     const size_t R = (size_t)b->m.n_robots;
-    c->hz.outs.add(b->m.pose_out, R * 24);
-    c->hz.outs.add(b->m.delta, R * 24);
-    c->hz.outs.add(b->m.best, R * 16);
-    c->hz.outs.add(b->m.n_valid, R * 8);
-    c->hz.outs.add(b->m.rot0, R * 16);
-    c->hz.outs.add(b->m.flags, R * 4);
-    c->hz.outs.add(b->m.scores, vol);
+    mapmatch_outs(c, &b->m, vol);
     c->hz.outs.add(b->P_out, R * 72);
     c->hz.outs.add(b->z, R * 24);
     c->hz.outs.add(b->Rm, R * 72);
@@ -1072,7 +1070,7 @@ static int launch_reloc_search(lslam_ctx *c, const RelocArgs &k, int nr) {
 }
 
 // The coarse stage in chunks of robots under the context's byte budget (search, peaks, the K best),
-// then K times the scan-to-map matcher as launch_mapmatch launches it, rank j's arrays in the place of
+// then K times the scan-to-map matcher (launch_mapmatch_kernels), rank j's arrays in the place of
 // the batch's, then the selection.  LSLAM_RELOC_FORM=add (tools/relocbench.py) selects the search
 // form that was measured and dropped.
 static int launch_reloc(lslam_ctx *c, const lslam_reloc_batch *b, const lslam_grid_params *g,
@@ -1152,9 +1150,7 @@ static int launch_reloc(lslam_ctx *c, const lslam_reloc_batch *b, const lslam_gr
         mb.rot0 = b->fine_rot0 + (size_t)j * Rz * 2;
         mb.flags = b->fine_flags + (size_t)j * Rz;
         if ((st = mapmatch_args(c, &mb, g, m, mk, mvol))) return st;  // (the stream orders the reuse of its scratch)
-        if ((st = launch_mapmatch_search(c, mk))) return st;
-        hipLaunchKernelGGL(mapmatch_pick_kernel, dim3((unsigned)R), dim3(MATCH_PICK_TPB), 0, c->stream, mk);
-        HIPCHK(hipGetLastError());
+        if ((st = launch_mapmatch_kernels(c, mk))) return st;
     }
     hipLaunchKernelGGL(reloc_select_kernel, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, c->stream, k);
     HIPCHK(hipGetLastError());
@@ -1385,9 +1381,9 @@ int lslam_map_match(lslam_ctx *c, const lslam_mapmatch_batch *b, const lslam_gri
     if (!b) return set_err(LSLAM_ERR_ARG, "mapmatch: batch is NULL");
     if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "mapmatch: negative n_robots");
     if (b->n_robots > 0) {
-        if (!b->xy || !b->pt_off || !b->pose || !b->origin || !b->logodds || !b->rot)
-            return set_err(LSLAM_ERR_ARG, "mapmatch: missing input (xy, pt_off, pose, origin, logodds, rot)");
-        if (!b->pose_out || !b->delta || !b->best || !b->n_valid || !b->rot0 || !b->flags)
+        const int miss = mapmatch_missing(b);
+        if (miss == 1) return set_err(LSLAM_ERR_ARG, "mapmatch: missing input (xy, pt_off, pose, origin, logodds, rot)");
+        if (miss == 2)
             return set_err(LSLAM_ERR_ARG, "mapmatch: missing output (pose_out, delta, best, n_valid, rot0, flags)");
     }
     if (!c) return set_err(LSLAM_ERR_ARG, "mapmatch: ctx is NULL");
@@ -1406,10 +1402,10 @@ int lslam_map_fuse(lslam_ctx *c, const lslam_mapfuse_batch *b, const lslam_grid_
     if (!b) return set_err(LSLAM_ERR_ARG, "mapfuse: batch is NULL");
     if (b->m.n_robots < 0) return set_err(LSLAM_ERR_ARG, "mapfuse: negative n_robots");
     if (b->m.n_robots > 0) {
-        if (!b->m.xy || !b->m.pt_off || !b->m.pose || !b->m.origin || !b->m.logodds || !b->m.rot || !b->P)
+        const int miss = mapmatch_missing(&b->m);
+        if (miss == 1 || !b->P)
             return set_err(LSLAM_ERR_ARG, "mapfuse: missing input (xy, pt_off, pose, origin, logodds, rot, P)");
-        if (!b->m.pose_out || !b->m.delta || !b->m.best || !b->m.n_valid || !b->m.rot0 || !b->m.flags || !b->P_out ||
-            !b->z || !b->Rm || !b->nis)
+        if (miss == 2 || !b->P_out || !b->z || !b->Rm || !b->nis)
             return set_err(LSLAM_ERR_ARG,
                            "mapfuse: missing output (pose_out, delta, best, n_valid, rot0, flags, P_out, z, Rm, nis)");
     }

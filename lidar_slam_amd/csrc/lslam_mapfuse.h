@@ -4,14 +4,13 @@
 // innovation, gate, Joseph-form update) is the comment on lslam_map_fuse in include/lidarslam.h;
 // tests/mapfuse_ref.py is its NumPy form.
 //
-// The score volume is mapmatch_search_kernel's, launched as it stands; lslam_mapmatch.h and
-// lslam_match.h are untouched and their device functions (match_key, match_refine, match_shfl_xor,
-// mapmatch_robot_cell, mapmatch_bits) are used here.
+// The score volume is mapmatch_search_kernel's (launch_mapmatch_search).  The winner's key, its
+// refinement and the match's flags are the functions mapmatch_pick_kernel calls: match_best,
+// match_winner (lslam_corr.h) and mapmatch_flags (lslam_mapmatch.h).
 //
 // Kernel:
-//   mapfuse_pick_kernel  one 256-thread workgroup per robot.  Pass 1 is mapmatch_pick_kernel's key
-//                        maximum; the four waves' maxima go through LDS and every thread takes
-//                        their maximum, which is the broadcast of the winner.  Pass 2 walks the
+//   mapfuse_pick_kernel  one 256-thread workgroup per robot.  Pass 1 is match_best, which leaves
+//                        the winner's key in every thread.  Pass 2 walks the
 //                        volume again (72 KB at the defaults: L2) and sums the ten int64 moments in
 //                        registers, over a wave by shuffles and over the four waves through LDS.
 //                        Thread 0 then runs steps 3-4 of the match and steps 6-8 of the fusion, a few
@@ -40,7 +39,7 @@ struct MapFuseArgs {
 };
 
 __device__ __forceinline__ long long mapfuse_shfl_xor(long long v, int o) {
-    return (long long)match_shfl_xor((unsigned long long)v, o);
+    return (long long)shfl_xor_u64((unsigned long long)v, o);
 }
 
 __device__ __forceinline__ unsigned long long mapfuse_word(double v) { return (unsigned long long)__double_as_longlong(v); }
@@ -73,29 +72,13 @@ __global__ __launch_bounds__(MATCH_PICK_TPB) void mapfuse_pick_kernel(const MapF
     __shared__ long long ws[NW][10];
     const MapMatchArgs &a = f.m;
     const int r = (int)blockIdx.x, tid = (int)threadIdx.x;
-    const int Nt = a.Nt, Nt2 = Nt * Nt, n = a.Nth * Nt2, kt = a.kt, kth = a.kth;
-    const int32_t *S = a.scores + (int64_t)r * n;
+    const CorrGeom &g = a.g;
+    const int n = g.Nth * g.Nt * g.Nt;
+    const int32_t *S = g.scores + (int64_t)r * n;
 
-    // ---- pass 1: the winner's key (mapmatch_pick_kernel's) ----
-    unsigned long long best = 0ull;
-    for (int i = tid; i < n; i += MATCH_PICK_TPB) {
-        const int k = i / Nt2, rem = i - k * Nt2, jy = rem / Nt, jx = rem - jy * Nt;
-        const int d2 = (k - kth) * (k - kth) + (jy - kt) * (jy - kt) + (jx - kt) * (jx - kt);
-        const unsigned long long key = match_key(S[i], d2, i);
-        best = key > best ? key : best;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long v = match_shfl_xor(best, o);
-        best = v > best ? v : best;
-    }
-    if ((tid & 63) == 0) wk[tid >> 6] = best;
-    __syncthreads();
-    best = wk[0];
-#pragma unroll
-    for (int w = 1; w < NW; w++) best = wk[w] > best ? wk[w] : best;
-    const int flat = 65535 - (int)(best & 0xffffull), s0 = (int)(best >> 27);
-    const int ks = flat / Nt2, jys = (flat - ks * Nt2) / Nt, jxs = flat - ks * Nt2 - jys * Nt;
+    // ---- pass 1: the winner's key ----
+    MatchWinner win = match_decode(g, match_best(g, S, wk, tid));
+    const int s0 = win.s0, ks = win.k, jys = win.jy, jxs = win.jx;
 
     // ---- pass 2 (step 5): the ten moments about the winner, int64 (each below 5e17) ----
     const long long cut = ((long long)s0 * (long long)f.cut_permille) / 1000ll;
@@ -105,7 +88,8 @@ __global__ __launch_bounds__(MATCH_PICK_TPB) void mapfuse_pick_kernel(const MapF
     for (int i = tid; i < n; i += MATCH_PICK_TPB) {
         const long long w = (long long)S[i] - cut;
         if (w <= 0) continue;
-        const int k = i / Nt2, rem = i - k * Nt2, jy = rem / Nt, jx = rem - jy * Nt;
+        int k, jy, jx;
+        match_unflat(g, i, k, jy, jx);
         const long long da = jx - jxs, db = jy - jys, dc = k - ks;
         const long long wa = w * da, wb = w * db, wc = w * dc;
         mo[0] += w;
@@ -155,29 +139,10 @@ __global__ __launch_bounds__(MATCH_PICK_TPB) void mapfuse_pick_kernel(const MapF
         P[i] = mapmatch_bits(Pb[i]);
     }
 
-    // ---- steps 3, 4 of lslam_map_match (mapmatch_pick_kernel's) ----
-    double X0d, Y0d;
-    const bool bad = !mapmatch_robot_cell(x[0], x[1], x[2], a.b.origin[2 * r], a.b.origin[2 * r + 1], a.inv, X0d, Y0d);
-    int k = ks, jy = jys, jx = jxs;
-    double y[3] = {0.0, 0.0, 0.0};
-    int flags = 0;
-    if (s0 == 0) {  // no valid point on an occupied cell (a bad pose's scores are zeros)
-        flags = bad ? LSLAM_MAPMATCH_BAD_POSE : LSLAM_MAPMATCH_EMPTY;
-        k = kth;
-        jy = kt;
-        jx = kt;
-    } else {
-        bool edge = false;
-        const double ex = match_refine(S, jx, Nt, flat, 1, s0, edge);
-        const double ey = match_refine(S, jy, Nt, flat, Nt, s0, edge);
-        const double et = match_refine(S, k, a.Nth, flat, Nt2, s0, edge);
-        y[0] = ((double)(jx - kt) + ex) * a.cell;
-        y[1] = ((double)(jy - kt) + ey) * a.cell;
-        y[2] = ((double)(k - kth) + et) * a.theta_step;
-        if (edge) flags |= LSLAM_MAPMATCH_EDGE;
-        const long long nv = (long long)a.b.n_valid[2 * r + 1];
-        if (1000ll * (long long)s0 < (long long)a.min_permille * (long long)(a.smear + 1) * nv) flags |= LSLAM_MAPMATCH_WEAK;
-    }
+    // ---- steps 3, 4 of lslam_map_match ----
+    match_winner(g, S, win);
+    const double (&y)[3] = win.d;
+    int flags = mapmatch_flags(a, r, win, x[0], x[1], x[2]);
 
     unsigned long long zb[3] = {xb[0], xb[1], xb[2]}, xo[3] = {xb[0], xb[1], xb[2]}, Po[9];
 #pragma unroll
@@ -191,7 +156,7 @@ __global__ __launch_bounds__(MATCH_PICK_TPB) void mapfuse_pick_kernel(const MapF
         // ---- step 6: the match covariance ----
         const double Wd = (double)mo[0];
         const double mean[3] = {(double)mo[1] / Wd, (double)mo[2] / Wd, (double)mo[3] / Wd};
-        const double sc[3] = {a.cell, a.cell, a.theta_step};
+        const double sc[3] = {g.cell, g.cell, g.theta_step};
         const long long m2[6] = {mo[4], mo[5], mo[6], mo[7], mo[8], mo[9]};  // aa ab ac bb bc cc
         int q = 0;
 #pragma unroll
@@ -262,12 +227,7 @@ __global__ __launch_bounds__(MATCH_PICK_TPB) void mapfuse_pick_kernel(const MapF
     }
 
     // ---- outputs: after every read of this robot's pose and P ----
-#pragma unroll
-    for (int i = 0; i < 3; i++) a.b.delta[3 * r + i] = y[i];
-    a.b.best[4 * r] = k;
-    a.b.best[4 * r + 1] = jy;
-    a.b.best[4 * r + 2] = jx;
-    a.b.best[4 * r + 3] = s0;
+    match_store(win, a.b.delta, a.b.best, r);
     a.b.flags[r] = flags;
     unsigned long long *pout = (unsigned long long *)a.b.pose_out + 3 * r, *zout = (unsigned long long *)f.z + 3 * r;
     unsigned long long *Pout = (unsigned long long *)f.P_out + 9 * r;

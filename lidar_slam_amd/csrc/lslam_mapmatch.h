@@ -4,10 +4,11 @@
 // lslam_map_match in include/lidarslam.h; tests/mapmatch_ref.py is its NumPy form.
 //
 // It is the correlative search of lslam_match.h with the map in the place of the previous
-// revolution, and shares that header's device code as it stands (match_planes, match_code,
-// MatchBytes, match_tile_task, match_key, match_refine and the LDS sizes); lslam_match.h itself is
-// untouched, so the two smear passes, which are written into match_search_kernel, are repeated
-// here as __device__ functions.
+// revolution, on the same core, lslam_corr.h: the LDS layout, the smear passes, match_tile_task, the
+// winner's key and the refinement are that header's.  This header holds the occupancy of G from the
+// map, the loop over rotations and tiles with its own point transform (match_search_kernel's loop
+// but for those lines), and the gate and pose_out; lslam_mapfuse.h and the fine stage of
+// lslam_reloc.h launch mapmatch_search_kernel and use mapmatch_flags.
 //
 // Kernels:
 //   mapmatch_search_kernel  one 512-thread workgroup per (robot, slice of rotations): builds the
@@ -16,11 +17,10 @@
 //   mapmatch_pick_kernel    one workgroup per robot: winner, parabola refinement, gate, flags and
 //                           pose_out
 //
-// LDS of mapmatch_search_kernel: the layout of match_search_kernel with win_w for grid_w -- G at
-// 2 bits per cell, W = win_w + 2 k_trans cells a side, rows of Sd dwords (Sd odd), then the staged
-// tile, the robot's six doubles of the point transform (pose, origin and robot cell: read back per
-// point, which keeps them out of the scalar registers that the search loop has none left of), four
-// counters and the rotation's scores: 78,356 B at the defaults, at most 81,836, two workgroups per CU.
+// LDS of mapmatch_search_kernel: lslam_corr.h's layout, and of its own the robot's six doubles of
+// the point transform between the staged tile and the counters (pose, origin and robot cell: read
+// back per point, which keeps them out of the scalar registers that the search loop has none left
+// of): 78,356 B at the defaults, at most 81,836, two workgroups per CU.
 //
 // Two parts differ from match_search_kernel:
 //   occupancy  the window's cells come from the robot's int16 grid.  The window's first column
@@ -35,13 +35,13 @@
 //              counted on the way (popcount), and slice 0 writes the sum.
 //   points     a point is rotated by the guess's heading composed with the rotation candidate,
 //              moved to the world frame and quantised in the map's grid; its offset from the robot
-//              cell is what match_search_kernel's robot-frame cell was.
+//              cell is what match_search_kernel's robot-frame cell is.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/lidarslam.h"
-#include "lslam_match.h"
+#include "lslam_corr.h"
 #include "lslam_wave.h"
 
 namespace lslam {
@@ -51,16 +51,10 @@ static inline int mapmatch_lds_bytes(int W, int Sd, int Nt) { return match_lds_b
 
 struct MapMatchArgs {
     lslam_mapmatch_batch b;
-    double inv, cell, theta_step;
+    CorrGeom g;     // win_w: the window's
     int map_w;      // cells per side of the map
-    int win_w, half, smear, kt, kth, Nt, Nth;
-    int W;          // win_w + 2 kt: cells a side with the apron
-    int Sd;         // dwords per row of G
-    int n_slices;   // workgroups per robot
-    int per_slice;  // rotations per workgroup
     int occ_min, min_permille;
     int vec;        // rows of logodds lie on 16-byte boundaries
-    int32_t *scores;  // [n_robots][Nth][Nt][Nt]: the caller's, or the context's scratch
 };
 
 // lslam_grid_update step 0: the robot cell as doubles, and whether the pose is usable
@@ -86,91 +80,24 @@ __device__ __forceinline__ uint32_t mapmatch_threshold8(uint4 v, int occ_min) {
     return m;
 }
 
-// The row pass of match_search_kernel: each thread sweeps whole rows of the window and leaves the
-// ROW value max(0, smear + 1 - |dx| to the nearest occupied cell of the row).
-__device__ __forceinline__ void mapmatch_smear_rows(uint32_t *G, int tid, int kt, int gw, int Sd, int sm) {
-    for (int row = kt + tid; row < kt + gw; row += MATCH_TPB) {
-        uint32_t *g = G + row * Sd;
-        uint32_t P = 0u, c = g[0];
-        for (int d = 0; d < Sd; d++) {
-            const uint32_t N = d + 1 < Sd ? g[d + 1] : 0u;
-            const uint32_t h1 = c | (c << 2) | (P >> 30) | (c >> 2) | (N << 30);
-            const uint32_t h2 = h1 | (c << 4) | (P >> 28) | (c >> 4) | (N << 28);
-            const uint32_t q1 = sm == 0 ? c : (sm == 1 ? h1 : h2);
-            const uint32_t q2 = sm == 0 ? 0u : (sm == 1 ? c : h1);
-            const uint32_t q3 = sm == 2 ? c : 0u;
-            g[d] = match_code(q1, q2, q3);
-            P = c;
-            c = N;
-        }
-    }
-}
-
-// The column pass of match_search_kernel (it holds a barrier: every thread of the workgroup calls
-// it): G = max over |dy| <= smear of min(row value(y + dy), smear + 1 - |dy|), the apron masked
-// back to zero.
-__device__ __forceinline__ void mapmatch_smear_cols(uint32_t *G, int tid, int kt, int gw, int W, int Sd, int sm) {
-    const int nseg = MATCH_TPB / Sd;  // Sd <= 35: at least 14 segments
-    const int seg_rows = (W + nseg - 1) / nseg;
-    const int col = tid % Sd, seg = tid / Sd;
-    const int y0 = seg * seg_rows, y1 = min(W, y0 + seg_rows);
-    const bool on = seg < nseg && y0 < y1;
-    uint32_t m2 = 0u, m1 = 0u, hp0 = 0u, hp1 = 0u;
-    if (on) {
-        if (y0 >= 2) m2 = G[(y0 - 2) * Sd + col];
-        if (y0 >= 1) m1 = G[(y0 - 1) * Sd + col];
-        if (y1 < W) hp0 = G[y1 * Sd + col];
-        if (y1 + 1 < W) hp1 = G[(y1 + 1) * Sd + col];
-    }
-    __syncthreads();
-    if (!on) return;
-    // cells of this dword column inside the window
-    const int lo = min(max(kt - col * 16, 0), 16), hi = min(max(kt + gw - col * 16, 0), 16);
-    const uint32_t mlo = lo >= 16 ? ~0u : ((1u << (2 * lo)) - 1u), mhi = hi >= 16 ? ~0u : ((1u << (2 * hi)) - 1u);
-    const uint32_t cmask = mhi & ~mlo;
-    uint32_t c = G[y0 * Sd + col];
-    uint32_t p1 = y0 + 1 < y1 ? G[(y0 + 1) * Sd + col] : hp0;
-    for (int y = y0; y < y1; y++) {
-        const int yn = y + 2;
-        const uint32_t p2 = yn < y1 ? G[yn * Sd + col] : (yn == y1 ? hp0 : hp1);
-        uint32_t a1, a2, a3, b1, b2, b3, c1, c2, c3, d1, d2, d3, e1, e2, e3;
-        match_planes(m2, a1, a2, a3);
-        match_planes(m1, b1, b2, b3);
-        match_planes(c, c1, c2, c3);
-        match_planes(p1, d1, d2, d3);
-        match_planes(p2, e1, e2, e3);
-        uint32_t q1 = c1, q2 = c2;
-        if (sm >= 1) q1 |= b1 | d1;
-        if (sm >= 2) {
-            q1 |= a1 | e1;
-            q2 |= b2 | d2;
-        }
-        const bool inrow = y >= kt && y < kt + gw;
-        G[y * Sd + col] = inrow ? (match_code(q1, q2, c3) & cmask) : 0u;
-        m2 = m1;
-        m1 = c;
-        c = p1;
-        p1 = p2;
-    }
-}
-
 __global__ __launch_bounds__(MATCH_TPB) void mapmatch_search_kernel(const MapMatchArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    const int W = a.W, Sd = a.Sd, kt = a.kt, half = a.half, ww = a.win_w, mw = a.map_w, sm = a.smear;
+    const CorrGeom &g = a.g;
+    const int W = g.W, Sd = g.Sd, kt = g.kt, half = g.half, ww = g.win_w, mw = a.map_w;
     const int S = Sd * 16;  // cells per row
     uint32_t *G = (uint32_t *)smem;
     uint32_t *stage = (uint32_t *)(smem + match_grid_bytes(W, Sd));
     double *wp = (double *)(stage + MATCH_TILE);  // px, py, ox, oy, X0, Y0
     int *cnt = (int *)(wp + 6);  // [0], [1]: the tile's lists; [2], [3]: occupied cells / valid points
     const int tid = (int)threadIdx.x;
-    const int r = (int)blockIdx.x / a.n_slices, slice = (int)blockIdx.x - r * a.n_slices;
-    const int Nt = a.Nt, Nt2 = Nt * Nt;
-    const int kbeg = slice * a.per_slice, kend = min(a.Nth, kbeg + a.per_slice);
+    const int r = (int)blockIdx.x / g.n_slices, slice = (int)blockIdx.x - r * g.n_slices;
+    const int Nt = g.Nt, Nt2 = Nt * Nt;
+    const int kbeg = slice * g.per_slice, kend = min(g.Nth, kbeg + g.per_slice);
 
     // ---- 0. pose, rotation, robot cell ----
     const double px = a.b.pose[3 * r], py = a.b.pose[3 * r + 1], th = a.b.pose[3 * r + 2];
     const double ox = a.b.origin[2 * r], oy = a.b.origin[2 * r + 1];
-    const double inv = a.inv;
+    const double inv = g.inv;
     const double c = cos(th), s = sin(th);  // (the same instructions in every workgroup: the same bits)
     if (slice == 0 && tid == 0) {
         a.b.rot0[2 * r] = c;
@@ -178,7 +105,7 @@ __global__ __launch_bounds__(MATCH_TPB) void mapmatch_search_kernel(const MapMat
     }
     double X0d, Y0d;
     if (!mapmatch_robot_cell(px, py, th, ox, oy, inv, X0d, Y0d)) {
-        int32_t *out = a.scores + ((int64_t)r * a.Nth + kbeg) * Nt2;
+        int32_t *out = g.scores + ((int64_t)r * g.Nth + kbeg) * Nt2;
         for (int i = tid; i < (kend - kbeg) * Nt2; i += MATCH_TPB) out[i] = 0;
         if (slice == 0 && tid < 2) a.b.n_valid[2 * r + tid] = 0;
         return;
@@ -224,9 +151,9 @@ __global__ __launch_bounds__(MATCH_TPB) void mapmatch_search_kernel(const MapMat
                         lc = 0;
                     }
                     const uint64_t w = (uint64_t)m << ((lc & 15) * 2);
-                    uint32_t *g = G + (my - wy0 + kt) * Sd + (lc >> 4);
-                    if ((uint32_t)w) atomicOr(g, (uint32_t)w);
-                    if ((uint32_t)(w >> 32)) atomicOr(g + 1, (uint32_t)(w >> 32));  // (a set bit there is a cell of this row)
+                    uint32_t *gd = G + (my - wy0 + kt) * Sd + (lc >> 4);
+                    if ((uint32_t)w) atomicOr(gd, (uint32_t)w);
+                    if ((uint32_t)(w >> 32)) atomicOr(gd + 1, (uint32_t)(w >> 32));  // (a set bit there is a cell of this row)
                 }
             } else {
                 const int ncols = mx1 - mx0;
@@ -250,9 +177,9 @@ __global__ __launch_bounds__(MATCH_TPB) void mapmatch_search_kernel(const MapMat
     if (slice == 0 && tid < 2) a.b.n_valid[2 * r + tid] = cnt[2 + tid];
 
     // ---- 2, 3. rows, columns ----
-    mapmatch_smear_rows(G, tid, kt, ww, Sd, sm);
+    corr_smear_rows(g, G, tid);
     __syncthreads();
-    mapmatch_smear_cols(G, tid, kt, ww, W, Sd, sm);
+    corr_smear_cols(g, G, tid);
     __syncthreads();
 
     // ---- search ----
@@ -303,68 +230,43 @@ __global__ __launch_bounds__(MATCH_TPB) void mapmatch_search_kernel(const MapMat
             if (pg < npg) match_tile_task(G, stage, cnt[0], cnt[1], pg, npg, lofs, jy, jxb, kt, Nt, S, W, sc);
         }
         __syncthreads();
-        int32_t *out = a.scores + ((int64_t)r * a.Nth + k) * Nt2;
+        int32_t *out = g.scores + ((int64_t)r * g.Nth + k) * Nt2;
         for (int i = tid; i < Nt2; i += MATCH_TPB) out[i] = sc[i];
     }
 }
 
 __device__ __forceinline__ double mapmatch_bits(unsigned long long v) { return __longlong_as_double((long long)v); }
 
+// Steps 3 and 4's flags of robot r's winner at pose (px, py, th): a score of 0 (no valid point on an
+// occupied cell; a bad pose's scores are zeros) is BAD_POSE or EMPTY, alone; otherwise EDGE, and
+// WEAK by the gate, in int64.  (Read after the search kernel: n_valid is final.)
+__device__ __forceinline__ int mapmatch_flags(const MapMatchArgs &a, int r, const MatchWinner &w, double px, double py,
+                                              double th) {
+    if (w.s0 == 0) {
+        double X0d, Y0d;
+        const bool ok = mapmatch_robot_cell(px, py, th, a.b.origin[2 * r], a.b.origin[2 * r + 1], a.g.inv, X0d, Y0d);
+        return ok ? LSLAM_MAPMATCH_EMPTY : LSLAM_MAPMATCH_BAD_POSE;
+    }
+    int flags = w.edge ? LSLAM_MAPMATCH_EDGE : 0;
+    const long long nv = (long long)a.b.n_valid[2 * r + 1];
+    if (1000ll * (long long)w.s0 < (long long)a.min_permille * (long long)(a.g.smear + 1) * nv) flags |= LSLAM_MAPMATCH_WEAK;
+    return flags;
+}
+
 __global__ __launch_bounds__(MATCH_PICK_TPB) void mapmatch_pick_kernel(const MapMatchArgs a) {
     __shared__ unsigned long long wk[MATCH_PICK_TPB / 64];
     const int r = (int)blockIdx.x, tid = (int)threadIdx.x;
-    const int Nt = a.Nt, Nt2 = Nt * Nt, n = a.Nth * Nt2, kt = a.kt, kth = a.kth;
-    const int32_t *S = a.scores + (int64_t)r * n;
-    unsigned long long best = 0ull;
-    for (int i = tid; i < n; i += MATCH_PICK_TPB) {
-        const int k = i / Nt2, rem = i - k * Nt2, jy = rem / Nt, jx = rem - jy * Nt;
-        const int d2 = (k - kth) * (k - kth) + (jy - kt) * (jy - kt) + (jx - kt) * (jx - kt);
-        const unsigned long long key = match_key(S[i], d2, i);
-        best = key > best ? key : best;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long v = match_shfl_xor(best, o);
-        best = v > best ? v : best;
-    }
-    if ((tid & 63) == 0) wk[tid >> 6] = best;
-    __syncthreads();
+    const CorrGeom &g = a.g;
+    const int32_t *S = g.scores + (int64_t)r * (g.Nth * g.Nt * g.Nt);
+    MatchWinner w = match_decode(g, match_best(g, S, wk, tid));
     if (tid != 0) return;
-    for (int w = 1; w < MATCH_PICK_TPB / 64; w++) best = wk[w] > best ? wk[w] : best;
     // this thread alone reads pose[r] and, below, writes pose_out[r]: they may be one buffer
     const unsigned long long *pin = (const unsigned long long *)a.b.pose + 3 * r;
     const unsigned long long bx = pin[0], by = pin[1], bt = pin[2];
     const double px = mapmatch_bits(bx), py = mapmatch_bits(by), th = mapmatch_bits(bt);
-    double X0d, Y0d;
-    const bool bad = !mapmatch_robot_cell(px, py, th, a.b.origin[2 * r], a.b.origin[2 * r + 1], a.inv, X0d, Y0d);
-    const int flat = 65535 - (int)(best & 0xffffull), s0 = (int)(best >> 27);
-    int k = flat / Nt2, jy = (flat - k * Nt2) / Nt, jx = flat - k * Nt2 - jy * Nt;
-    double dx = 0.0, dy = 0.0, dth = 0.0;
-    int flags = 0;
-    if (s0 == 0) {  // no valid point on an occupied cell (a bad pose's scores are zeros)
-        flags = bad ? LSLAM_MAPMATCH_BAD_POSE : LSLAM_MAPMATCH_EMPTY;
-        k = kth;
-        jy = kt;
-        jx = kt;
-    } else {
-        bool edge = false;
-        const double ex = match_refine(S, jx, Nt, flat, 1, s0, edge);
-        const double ey = match_refine(S, jy, Nt, flat, Nt, s0, edge);
-        const double et = match_refine(S, k, a.Nth, flat, Nt2, s0, edge);
-        dx = ((double)(jx - kt) + ex) * a.cell;
-        dy = ((double)(jy - kt) + ey) * a.cell;
-        dth = ((double)(k - kth) + et) * a.theta_step;
-        if (edge) flags |= LSLAM_MAPMATCH_EDGE;
-        const long long nv = (long long)a.b.n_valid[2 * r + 1];
-        if (1000ll * (long long)s0 < (long long)a.min_permille * (long long)(a.smear + 1) * nv) flags |= LSLAM_MAPMATCH_WEAK;
-    }
-    a.b.delta[3 * r] = dx;
-    a.b.delta[3 * r + 1] = dy;
-    a.b.delta[3 * r + 2] = dth;
-    a.b.best[4 * r] = k;
-    a.b.best[4 * r + 1] = jy;
-    a.b.best[4 * r + 2] = jx;
-    a.b.best[4 * r + 3] = s0;
+    match_winner(g, S, w);
+    const int flags = mapmatch_flags(a, r, w, px, py, th);
+    match_store(w, a.b.delta, a.b.best, r);
     a.b.flags[r] = flags;
     if (flags & (LSLAM_MAPMATCH_EMPTY | LSLAM_MAPMATCH_BAD_POSE | LSLAM_MAPMATCH_WEAK)) {
         unsigned long long *pout = (unsigned long long *)a.b.pose_out + 3 * r;
@@ -372,9 +274,9 @@ __global__ __launch_bounds__(MATCH_PICK_TPB) void mapmatch_pick_kernel(const Map
         pout[1] = by;
         pout[2] = bt;
     } else {
-        a.b.pose_out[3 * r] = px + dx;
-        a.b.pose_out[3 * r + 1] = py + dy;
-        a.b.pose_out[3 * r + 2] = th + dth;
+        a.b.pose_out[3 * r] = px + w.d[0];
+        a.b.pose_out[3 * r + 1] = py + w.d[1];
+        a.b.pose_out[3 * r + 2] = th + w.d[2];
     }
 }
 

@@ -12,7 +12,9 @@
 //   reloc_topk_kernel    one workgroup per robot: the K best keys of all its blocks, cand, cand_pose
 //   reloc_select_kernel  one thread per robot: the winner among the refined ranks, the ambiguity
 //                        test, pose_out and P_out
-// The fine stage between the last two is mapmatch_search_kernel + mapmatch_pick_kernel as they stand.
+// The fine stage between the last two is the scan-to-map matcher's two kernels (launch_mapmatch_kernels),
+// once per rank.  The coarse search is another algorithm than lslam_corr.h's (bit-sliced counters over
+// a one-bit map, no smear); of that header it uses the block-wide key maximum, corr_block_max.
 //
 // reloc_search_kernel.  The bitmap holds one bit per coarse cell, Wc zero bits left of each row and
 // at least Wc right of it, in rows of RW dwords (RW odd: consecutive rows start on different banks),
@@ -246,19 +248,10 @@ __device__ __forceinline__ unsigned long long reloc_key(int score, int flat) {
     return ((unsigned long long)(uint32_t)score << 32) | (unsigned long long)(0xffffffffu - (uint32_t)flat);
 }
 
-// the largest key of the workgroup (every thread calls it; wk: one slot per wave)
+// the largest key of the workgroup in a loop of rounds (every thread calls it; wk: one slot per wave)
 __device__ __forceinline__ unsigned long long reloc_block_max(unsigned long long v, unsigned long long *wk, int tid) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned long long u = match_shfl_xor(v, o);
-        v = u > v ? u : v;
-    }
     __syncthreads();  // the previous round's readers are done
-    if ((tid & 63) == 0) wk[tid >> 6] = v;
-    __syncthreads();
-    v = wk[0];
-    for (int w = 1; w < RELOC_PEAK_TPB / 64; w++) v = wk[w] > v ? wk[w] : v;
-    return v;
+    return corr_block_max<RELOC_PEAK_TPB / 64>(v, wk, tid);
 }
 
 __global__ __launch_bounds__(RELOC_PEAK_TPB) void reloc_peak_kernel(const RelocArgs a) {

@@ -1,7 +1,11 @@
-"""The relocalisation kernels keep their counters in registers: no spills, no scratch (CPU test: needs
-hipcc's llvm-readelf, no GPU).  The search kernel's 32 sums, 8 planes and 8 windows per thread must fit
-the 128 VGPRs of a 512-thread workgroup; its LDS is dynamic (lslam_reloc.h).  DESIGN §4.4 quotes the
-counts."""
+"""The matcher, match-fusion and relocalisation kernels keep what they hold in registers: no spills, no
+scratch (CPU test: needs hipcc's llvm-readelf, no GPU).  DESIGN §4.4 quotes the counts.
+
+The two search kernels of the correlative matcher (lslam_corr.h's loop) run at the edge of the scalar
+registers, 106 of them in the scan matcher's loop, so a spill is what a change to the shared code would
+show first; two 512-thread workgroups per CU, which their LDS sizes assume, leave a wave 128 VGPRs.
+The match-fusion kernel holds ten 64-bit sums and the 3x3 matrices of thread 0; the relocalisation
+search holds 32 sums, 8 planes and 8 windows per thread.  The search kernels' LDS is dynamic."""
 import os
 import re
 import shutil
@@ -12,6 +16,11 @@ import pytest
 LLVM = "/opt/rocm/lib/llvm/bin"
 # kernel -> (most VGPRs, static LDS bytes)
 KERNELS = {
+    "_ZN5lslam19match_search_kernelENS_9MatchArgsE": (128, 0),
+    "_ZN5lslam17match_pick_kernelENS_9MatchArgsE": (128, 32),
+    "_ZN5lslam22mapmatch_search_kernelENS_12MapMatchArgsE": (128, 0),
+    "_ZN5lslam20mapmatch_pick_kernelENS_12MapMatchArgsE": (128, 32),
+    "_ZN5lslam19mapfuse_pick_kernelILi0EEEvNS_11MapFuseArgsE": (128, 352),
     "_ZN5lslam19reloc_search_kernelILi0EEEvNS_9RelocArgsE": (128, 0),
     "_ZN5lslam19reloc_search_kernelILi1EEEvNS_9RelocArgsE": (128, 0),
     "_ZN5lslam17reloc_peak_kernelENS_9RelocArgsE": (128, 32),
@@ -25,7 +34,7 @@ pytestmark = pytest.mark.skipif(not os.path.exists(os.path.join(LLVM, "llvm-read
 @pytest.fixture(scope="module")
 def notes(tmp_path_factory):
     from lidar_slam_amd import build
-    tmp = str(tmp_path_factory.mktemp("reloc_budget"))
+    tmp = str(tmp_path_factory.mktemp("kernel_budget"))
     so = os.path.join(tmp, "lib.so")
     shutil.copy(build.build(verbose=False), so)
     subprocess.check_call([os.path.join(LLVM, "llvm-objdump"), "--offloading", so], cwd=tmp,
@@ -38,7 +47,7 @@ def notes(tmp_path_factory):
 
 
 @pytest.mark.parametrize("symbol", sorted(KERNELS))
-def test_reloc_kernel_has_no_spills_and_no_scratch(notes, symbol):
+def test_kernel_has_no_spills_and_no_scratch(notes, symbol):
     max_vgpr, lds = KERNELS[symbol]
     mine = [b for b in notes if re.search(r"\.name:\s+%s\s" % re.escape(symbol), b)]
     assert len(mine) == 1, "%s is missing from the code object" % symbol
