@@ -429,6 +429,53 @@ typedef struct lslam_reloc_batch {
     int32_t *coarse_scores;   /* [n_robots][n_head][Wc][Wc] the whole coarse volume (optional) */
 } lslam_reloc_batch;
 
+/* ---- grid ray-cast flags (lslam_raycast_batch.flags), beam classes and stop kinds (cls) ---- */
+enum {
+    LSLAM_RAYCAST_BAD_POSE = 1  /* as LSLAM_GRID_BAD_POSE: nothing is cast */
+};
+enum {
+    LSLAM_RAYCAST_INVALID = 0,   /* not a valid point (or a denormal one): nothing is cast */
+    LSLAM_RAYCAST_MATCH = 1,     /* the beam returned where the map says it stops */
+    LSLAM_RAYCAST_NOVEL = 2,     /* a return inside space the map holds free: a dynamic object */
+    LSLAM_RAYCAST_THROUGH = 3,   /* the beam passed a cell the map holds occupied: a stale map or a wrong pose */
+    LSLAM_RAYCAST_UNMAPPED = 4   /* the beam ran into unknown space at or before its return */
+};
+enum {
+    LSLAM_RAYCAST_KIND_NONE = 0,     /* the ray left the range circle still free */
+    LSLAM_RAYCAST_KIND_UNKNOWN = 1,  /* it stopped at an unknown cell, or off the map */
+    LSLAM_RAYCAST_KIND_OCC = 2       /* it stopped at an occupied cell */
+};
+
+/* Grid ray casting (lslam_grid_raycast), 16 bytes.  The grid's geometry comes from the
+ * lslam_grid_params given with the call. */
+typedef struct lslam_raycast_params {
+    int32_t occ_min;   /* a cell is occupied iff L >= occ_min; -32768..32767 (1: more hits than passes, p > 0.5) */
+    int32_t free_max;  /* a cell is free iff L <= free_max; -32768..32766 and < occ_min (-1: p < 0.5; L = 0 alone
+                          is unknown.  The matchers' 85 and one pass's -41 leave the cells beside a wall,
+                          one hit and a few passes, unknown: DESIGN.md 4.4) */
+    int32_t tol;       /* tolerance in steps along the ray, 0..64 (3) */
+    int32_t reserved;
+} lslam_raycast_params;
+
+/* One revolution per robot cast through the robot's grid, 88 bytes; all pointers DEVICE memory, all
+ * required but stop.  P = pt_off[n_robots]. */
+typedef struct lslam_raycast_batch {
+    int32_t n_robots;
+    int32_t reserved;
+    /* inputs */
+    const double *xy;         /* [P][2] revolutions, each in its robot's frame */
+    const int32_t *pt_off;    /* [n_robots+1] CSR robot -> points */
+    const double *pose;       /* [n_robots][3] (x mm, y mm, theta rad), e.g. the filter's ukf_x */
+    const double *origin;     /* [n_robots][2] world coordinates of the corner of cell (0, 0) */
+    const int16_t *logodds;   /* [n_robots][grid_w][grid_w], row Y: read only */
+    /* outputs */
+    uint8_t *cls;             /* [P] class | kind << 4 */
+    int32_t *stop;            /* [P][3] (ox, oy, i_h): where the map stops the beam, in cells from the robot cell (optional) */
+    int32_t *counts;          /* [n_robots][8] points of classes 0..4, valid points beyond max_range, points of kind NONE, 0 */
+    double *rot;              /* [n_robots][2] (cos theta, sin theta) as used */
+    int32_t *flags;           /* [n_robots] LSLAM_RAYCAST_* */
+} lslam_raycast_batch;
+
 typedef struct lslam_ctx lslam_ctx;  /* opaque: device, stream, events, scratch */
 
 /* ---- library / context ---- */
@@ -471,6 +518,8 @@ int lslam_mapmatch_abi_sizes(int64_t *sizes, int n);
 int lslam_mapfuse_abi_sizes(int64_t *sizes, int n);
 /* and for lslam_reloc_params, lslam_reloc_batch.  Writes min(n, 2) entries, returns 2. */
 int lslam_reloc_abi_sizes(int64_t *sizes, int n);
+/* and for lslam_raycast_params, lslam_raycast_batch.  Writes min(n, 2) entries, returns 2. */
+int lslam_raycast_abi_sizes(int64_t *sizes, int n);
 /* per-kernel HIP-event timing on the ctx stream (kernel ids: LSLAM_K_*) */
 enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMARK = 3, LSLAM_K_UKF = 4,
        LSLAM_K_RNG = 5 /* parity-stream producer */, LSLAM_K_CONSENSUS = 6 /* per-chunk A4-A8 */,
@@ -478,7 +527,8 @@ enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMAR
        LSLAM_K_EXPRESS_SCATTER = 8 /* its decode + A1 + scatter kernel */,
        LSLAM_K_MATCH = 9 /* a whole scan-match call */, LSLAM_K_GRID = 10 /* a whole grid update */,
        LSLAM_K_MAPMATCH = 11 /* a whole scan-to-map call */, LSLAM_K_MAPFUSE = 12 /* a whole match-fusion call */,
-       LSLAM_K_RELOC = 13 /* a whole relocalisation call */, LSLAM_K_COUNT = 14 };
+       LSLAM_K_RELOC = 13 /* a whole relocalisation call */, LSLAM_K_RAYCAST = 14 /* a whole grid ray-cast call */,
+       LSLAM_K_COUNT = 15 };
 int lslam_set_timing(lslam_ctx *ctx, int enable);
 /* which kernel ids are timed while timing is on (bit k = LSLAM_K_k; default all).  Timing
  * events between the producer and consumer kernels change how the two streams overlap,
@@ -505,6 +555,7 @@ int lslam_grid_params_default(lslam_grid_params *p);
 int lslam_mapmatch_params_default(lslam_mapmatch_params *p);
 int lslam_mapfuse_params_default(lslam_mapfuse_params *p);
 int lslam_reloc_params_default(lslam_reloc_params *p);
+int lslam_raycast_params_default(lslam_raycast_params *p);
 /* smallest e with RN(sqrt(e)) >= thr: (residual < thr) <=> (squared residual < cutoff) */
 double lslam_inlier_cutoff(double thr);
 /* MerweScaledSigmaPoints weights (filterpy _compute_weights) for n = 3 */
@@ -739,6 +790,53 @@ int lslam_map_fuse(lslam_ctx *ctx, const lslam_mapfuse_batch *b, const lslam_gri
  * the context is touched; n_robots == 0 does nothing. */
 int lslam_map_relocalize(lslam_ctx *ctx, const lslam_reloc_batch *b, const lslam_grid_params *g,
                          const lslam_mapmatch_params *m, const lslam_reloc_params *q);
+
+/* Grid ray casting: one revolution per robot, the robot's pose and its log-odds grid -> for every beam
+ * where the MAP says it stops, and how that compares with where it returned.  The read side of
+ * lslam_grid_update: the same pose, points and integer ray, walked until the map ends it.  The grid's
+ * geometry is g's cell, grid_w and max_range (g is checked as lslam_grid_update checks it).  A cell is
+ * occupied iff L >= occ_min, free iff L <= free_max; every other cell, and every cell off the map, is
+ * unknown.  Per robot r, in FP64 with every operation rounded on its own, then integers;
+ * inv = 1.0 / cell:
+ *   0. pose, rotation and robot cell: step 0 of lslam_grid_update, verbatim; (c, s) go to rot[r]
+ *      (always) and the written bits are the definition's input.  X0d = floor((px - ox) inv),
+ *      Y0d = floor((py - oy) inv) as doubles, (X0, Y0) as integers.  A bad pose (that step's condition)
+ *      gives flags[r] = LSLAM_RAYCAST_BAD_POSE, cls = 0 and stop = (0, 0, 0) for every point of the
+ *      robot, and counts[r] all zero.  Otherwise flags[r] = 0.
+ *   1. points: valid as in lslam_scan_match (both coordinates finite, not exactly (0, 0)); an invalid
+ *      point has cls = LSLAM_RAYCAST_INVALID and stop = (0, 0, 0).  A valid point is beyond iff
+ *      x x + y y > max_range max_range.  A valid point that is not beyond has the measured hit cell
+ *      (X1, Y1) of lslam_grid_update step 1, and its measured step i_m = max(|X1 - X0|, |Y1 - Y0|).
+ *   2. far cell of the beam: m = max(|x|, |y|), far = max_range + 2.0 cell, q = far / m, fx = x q,
+ *      fy = y q: the beam scaled to the square of half side far, its exact direction for one division.
+ *      wx = px + (c fx - s fy), wy = py + (s fx + c fy), XFd = floor((wx - ox) inv),
+ *      YFd = floor((wy - oy) inv), Dxd = XFd - X0d, Dyd = YFd - Y0d, all doubles.  If Dxd or Dyd is
+ *      not finite or exceeds 8192 in magnitude (a denormal point: q overflows) the point is INVALID as
+ *      in step 1.  Otherwise Dx = (int)Dxd, Dy = (int)Dyd, n = max(|Dx|, |Dy|).
+ *   3. walk i = 0 .. n.  The offset at step i is (ox, oy) = (sgn(Dx) ((2 i |Dx| + n) div 2n),
+ *      sgn(Dy) ((2 i |Dy| + n) div 2n)), the ray of lslam_grid_update step 2; n = 0 means i = 0 only,
+ *      offset (0, 0).  Rc = (int)floor(max_range inv).  The walk stops at the first step that meets
+ *      one of these, tested in this order:
+ *        ox ox + oy oy > Rc Rc                      kind NONE: the ray left the range circle still free
+ *        the cell (X0 + ox, Y0 + oy) is occupied    kind OCC
+ *        it is unknown, or off the map              kind UNKNOWN
+ *      and i_h is that step.  If no step stops it: kind NONE, i_h = n + 1, (ox, oy) of step n.
+ *      stop[p] = (ox, oy, i_h).  (|ox|, |oy| <= 8192 keeps every product inside int32.)
+ *   4. class, in integers; i_m counts as +infinity for a beyond point:
+ *        OCC      i_m < i_h - tol: NOVEL;  i_m > i_h + tol: THROUGH;  otherwise MATCH
+ *        UNKNOWN  i_m < i_h - tol: NOVEL;  otherwise UNMAPPED
+ *        NONE     beyond, or i_m >= i_h - tol: MATCH;  otherwise NOVEL
+ *      cls[p] = class | kind << 4.
+ *   5. counts[r] = (points of class 0, 1, 2, 3, 4, points that are beyond and not INVALID, points of
+ *      kind NONE that are not INVALID, 0): integers, so the order of accumulation does not matter.
+ * The expected range of a beam of kind OCC is cell hypot(ox, oy).  To render the map as a scan, pass
+ * unit vectors times max_range: stop is the answer and the classes are ignored.
+ * Runs on the context's main stream, after every earlier call: it sees the ukf_x of a preceding
+ * lslam_scan_pipeline and the grid of a preceding lslam_grid_update.  Out-of-range parameters and
+ * missing pointers return LSLAM_ERR_ARG (the message names the field), checked before the context is
+ * touched; n_robots == 0 does nothing. */
+int lslam_grid_raycast(lslam_ctx *ctx, const lslam_raycast_batch *b, const lslam_grid_params *g,
+                       const lslam_raycast_params *p);
 
 #ifdef __cplusplus
 }

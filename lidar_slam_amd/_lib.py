@@ -30,11 +30,15 @@ HYP_MT19937, HYP_PHILOX, HYP_EXPLICIT = 0, 1, 2
 UKF_PREDICT, UKF_UPDATE, UKF_LMK_FROM_RANSAC, UKF_MAP, UKF_SIGMAS_IN = 1, 2, 4, 8, 16
 K_POLAR, K_HYP, K_PIPELINE, K_LANDMARK, K_UKF, K_RNG, K_CONSENSUS = 0, 1, 2, 3, 4, 5, 6
 K_EXPRESS, K_EXPRESS_SCATTER, K_MATCH, K_GRID, K_MAPMATCH, K_MAPFUSE, K_RELOC = 7, 8, 9, 10, 11, 12, 13
+K_RAYCAST = 14
 MATCH_EMPTY, MATCH_EDGE = 1, 2
 GRID_BAD_POSE, GRID_CLIPPED = 1, 2
 MAPMATCH_EMPTY, MAPMATCH_EDGE, MAPMATCH_BAD_POSE, MAPMATCH_WEAK = 1, 2, 4, 8
 MAPFUSE_OUTLIER, MAPFUSE_BAD_COV = 16, 32
 RELOC_LOST, RELOC_AMBIGUOUS = 1, 2
+RAYCAST_BAD_POSE = 1
+RAYCAST_INVALID, RAYCAST_MATCH, RAYCAST_NOVEL, RAYCAST_THROUGH, RAYCAST_UNMAPPED = 0, 1, 2, 3, 4  # cls & 15
+RAYCAST_KIND_NONE, RAYCAST_KIND_UNKNOWN, RAYCAST_KIND_OCC = 0, 1, 2  # cls >> 4
 
 
 class HIPLibraryError(RuntimeError):
@@ -139,6 +143,15 @@ class RelocBatch(C.Structure):
                                    "fine_flags", "result", "flags", "pose_out", "P_out", "coarse_scores")]
 
 
+class RaycastParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("occ_min", "free_max", "tol", "reserved")]
+
+
+class RaycastBatch(C.Structure):
+    _fields_ = [("n_robots", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, _VP) for n in ("xy", "pt_off", "pose", "origin", "logodds", "cls", "stop", "counts", "rot", "flags")]
+
+
 assert C.sizeof(ChunkModel) == 112
 assert C.sizeof(LandmarkRec) == 56
 
@@ -156,6 +169,7 @@ EXPORTS = [
     "lslam_mapmatch_abi_sizes", "lslam_mapmatch_params_default", "lslam_map_match",
     "lslam_mapfuse_abi_sizes", "lslam_mapfuse_params_default", "lslam_map_fuse",
     "lslam_reloc_abi_sizes", "lslam_reloc_params_default", "lslam_map_relocalize", "lslam_set_reloc_budget",
+    "lslam_raycast_abi_sizes", "lslam_raycast_params_default", "lslam_grid_raycast",
 ]
 
 _lib = None
@@ -234,6 +248,9 @@ def load():
         "lslam_reloc_params_default": ([P(RelocParams)], C.c_int),
         "lslam_map_relocalize": ([_VP, P(RelocBatch), P(GridParams), P(MapMatchParams), P(RelocParams)], C.c_int),
         "lslam_set_reloc_budget": ([_VP, i64], C.c_int),
+        "lslam_raycast_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_raycast_params_default": ([P(RaycastParams)], C.c_int),
+        "lslam_grid_raycast": ([_VP, P(RaycastBatch), P(GridParams), P(RaycastParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -272,9 +289,12 @@ def _check_abi(L):
     L.lslam_mapfuse_abi_sizes(got4, 2)
     got5 = (C.c_int64 * 2)()
     L.lslam_reloc_abi_sizes(got5, 2)
-    got = list(got) + list(got2) + list(got3) + list(got4) + list(got5)
+    got6 = (C.c_int64 * 2)()
+    L.lslam_raycast_abi_sizes(got6, 2)
+    got = list(got) + list(got2) + list(got3) + list(got4) + list(got5) + list(got6)
     want = want + [C.sizeof(GridParams), C.sizeof(GridBatch), C.sizeof(MapMatchParams), C.sizeof(MapMatchBatch),
-                   C.sizeof(MapFuseParams), C.sizeof(MapFuseBatch), C.sizeof(RelocParams), C.sizeof(RelocBatch)]
+                   C.sizeof(MapFuseParams), C.sizeof(MapFuseBatch), C.sizeof(RelocParams), C.sizeof(RelocBatch),
+                   C.sizeof(RaycastParams), C.sizeof(RaycastBatch)]
     if list(got) != want:
         _err = HIPLibraryError("struct sizes differ between %s %s and the ctypes layouts %s"
                                % (LIB_PATH, list(got), want))
@@ -363,6 +383,14 @@ def mapfuse_params(**kw):
 def reloc_params(**kw):
     p = RelocParams()
     load().lslam_reloc_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def raycast_params(**kw):
+    p = RaycastParams()
+    load().lslam_raycast_params_default(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

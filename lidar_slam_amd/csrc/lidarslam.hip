@@ -9,7 +9,8 @@
 //   lslam_match.h (the scan matcher's two kernels), lslam_grid.h
 //   (the occupancy-grid kernel; its integer ray is lslam_grid_ray.h, plain C++), lslam_mapmatch.h
 //   (the scan-to-map matcher's two kernels), lslam_mapfuse.h (the match-fusion kernel),
-//   lslam_reloc.h (the relocalisation kernels);
+//   lslam_reloc.h (the relocalisation kernels), lslam_raycast.h (the grid ray-cast kernel; one
+//   beam's walk is lslam_raycast_walk.h, plain C++);
 // the host side is included at the foot:
 //   lslam_hazards.h  which waits a call's producer needs (plain C++, no HIP)
 //   lslam_ctx.h      lslam_ctx, its grow-only device buffers and timers, create / destroy,
@@ -3057,6 +3058,8 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
 #include "lslam_mapfuse.h"
 // the relocalisation kernels, after those: a coarse search of their own around the scan-to-map matcher
 #include "lslam_reloc.h"
+// the grid ray-cast kernel, last: the walk of lslam_raycast_walk.h through a window of the grid
+#include "lslam_raycast.h"
 
 // ------------------------------------------------------------------------
 // host side: the context, then the launchers and entry points

@@ -397,6 +397,12 @@ int lslam_reloc_abi_sizes(int64_t *sizes, int n) {
     return 2;
 }
 
+int lslam_raycast_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[2] = {(int64_t)sizeof(lslam_raycast_params), (int64_t)sizeof(lslam_raycast_batch)};
+    for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
+    return 2;
+}
+
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
     if (!c || (!dst && n)) return LSLAM_ERR_ARG;
     if (!n) return LSLAM_OK;
@@ -560,6 +566,18 @@ int lslam_reloc_params_default(lslam_reloc_params *p) {
     p->dup_rad = 0.0873;                 // five degrees
     p->reset_sigma_xy = 50.0;            // mm
     p->reset_sigma_theta = 0.05;         // rad
+    return LSLAM_OK;
+}
+
+int lslam_raycast_params_default(lslam_raycast_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    // a cell with any net evidence is read: p > 0.5 occupied, p < 0.5 free, L = 0 (never seen) unknown.  The
+    // matchers' 85 with one pass's -41 calls the cells beside a wall (one hit, a few passes) unknown, and
+    // they stop 28 % of a room's beams in front of the wall
+    p->occ_min = 1;
+    p->free_max = -1;
+    p->tol = 3;         // steps: the map's walls are one to two cells thick
     return LSLAM_OK;
 }
 

@@ -1174,6 +1174,67 @@ static int launch_reloc(lslam_ctx *c, const lslam_reloc_batch *b, const lslam_gr
     return LSLAM_OK;
 }
 
+// ---- grid ray casting (lslam_raycast.h) ----
+
+static int raycast_check_params(const lslam_raycast_params *p) {
+    if (!p) return set_err(LSLAM_ERR_ARG, "raycast: params is NULL");
+    if (p->occ_min < -32768 || p->occ_min > 32767)
+        return set_err(LSLAM_ERR_ARG, "raycast: occ_min must be in [-32768, 32767]");
+    if (p->free_max < -32768 || p->free_max > 32766 || p->free_max >= p->occ_min)
+        return set_err(LSLAM_ERR_ARG, "raycast: free_max must be in [-32768, 32766] and below occ_min");
+    if (p->tol < 0 || p->tol > 64) return set_err(LSLAM_ERR_ARG, "raycast: tol must be in [0, 64]");
+    return LSLAM_OK;
+}
+
+template <int FORM>
+static int launch_raycast_form(lslam_ctx *c, const RaycastArgs &k, int lds) {
+    static std::once_flag once;
+    std::call_once(once, [] { set_max_lds(raycast_kernel<FORM>); });
+    hipLaunchKernelGGL(raycast_kernel<FORM>, dim3((unsigned)((int64_t)k.b.n_robots * k.n_slices)), dim3(RAYCAST_TPB), lds,
+                       c->stream, k);
+    HIPCHK(hipGetLastError());
+    return LSLAM_OK;
+}
+
+// One workgroup per (robot, slice of its points), by launch_mapmatch's rule: slices exist so that a
+// few robots still fill the chip.  The HBM form ships: in the bench room's grids it is the faster one
+// at 4096 robots.  LSLAM_RAYCAST_FORM=lds (tools/raycastbench.py, the tests) selects
+// the LDS form where the largest window's codes fit its budget.
+static int launch_raycast(lslam_ctx *c, const lslam_raycast_batch *b, const lslam_grid_params *g,
+                          const lslam_raycast_params *p) {
+    RaycastArgs k;
+    memset(&k, 0, sizeof(k));
+    k.b = *b;
+    k.inv = 1.0 / g->cell;
+    k.max_r2 = g->max_range * g->max_range;
+    k.far = g->max_range + 2.0 * g->cell;
+    k.grid_w = g->grid_w;
+    k.Rc = (int)floor(g->max_range * k.inv);
+    k.occ_min = p->occ_min;
+    k.free_max = p->free_max;
+    k.tol = p->tol;
+    k.vec = (g->grid_w % 8 == 0 && ((uintptr_t)b->logodds & 15) == 0) ? 1 : 0;
+    const int win = raycast_window(k.Rc, k.grid_w);
+    k.Sd = raycast_row_dwords(win);
+    int hbm = 1;
+    if (const char *e = getenv("LSLAM_RAYCAST_FORM"))
+        if (!strcmp(e, "lds") && raycast_lds_bytes(win) <= RAYCAST_LDS_BUDGET) hbm = 0;
+    const int64_t n = b->n_robots, want = 2 * (int64_t)c->n_cus;
+    k.n_slices = (int)std::min<int64_t>(std::max<int64_t>((want + n - 1) / n, 1), RAYCAST_MAX_SLICES);
+    if (n * k.n_slices >= ((int64_t)1 << 31)) return set_err(LSLAM_ERR_UNSUPPORTED, "raycast: too many robots in one call");
+    int st = timer_begin(c, LSLAM_K_RAYCAST);
+    if (st) return st;
+    HIPCHK(hipMemsetAsync(b->counts, 0, (size_t)n * 32, c->stream));
+    st = hbm ? launch_raycast_form<1>(c, k, 32) : launch_raycast_form<0>(c, k, raycast_lds_bytes(win));
+    if (st) return st;
+    if ((st = timer_end(c, LSLAM_K_RAYCAST))) return st;
+    // (cls and stop are as long as pt_off, on the device, says: per-point outputs that no producer reads)
+    c->hz.outs.add(b->counts, (size_t)n * 32);
+    c->hz.outs.add(b->rot, (size_t)n * 16);
+    c->hz.outs.add(b->flags, (size_t)n * 4);
+    return LSLAM_OK;
+}
+
 // ---- express-scan codec (lslam_express.h) ----
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1437,6 +1498,26 @@ int lslam_map_relocalize(lslam_ctx *c, const lslam_reloc_batch *b, const lslam_g
     if (b->n_robots == 0) return LSLAM_OK;
     HIPCHK(hipSetDevice(c->device));
     return launch_reloc(c, b, g, m, q);
+}
+
+// On the main stream, as lslam_map_match.
+int lslam_grid_raycast(lslam_ctx *c, const lslam_raycast_batch *b, const lslam_grid_params *g,
+                       const lslam_raycast_params *p) {
+    int st = raycast_check_params(p);
+    if (st) return st;
+    if ((st = grid_check_params(g))) return st;
+    if (!b) return set_err(LSLAM_ERR_ARG, "raycast: batch is NULL");
+    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "raycast: negative n_robots");
+    if (b->n_robots > 0) {
+        if (!b->xy || !b->pt_off || !b->pose || !b->origin || !b->logodds)
+            return set_err(LSLAM_ERR_ARG, "raycast: missing input (xy, pt_off, pose, origin, logodds)");
+        if (!b->cls || !b->counts || !b->rot || !b->flags)
+            return set_err(LSLAM_ERR_ARG, "raycast: missing output (cls, counts, rot, flags)");
+    }
+    if (!c) return set_err(LSLAM_ERR_ARG, "raycast: ctx is NULL");
+    if (b->n_robots == 0) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return launch_raycast(c, b, g, p);
 }
 
 // (the scratch is sized per call: a call in flight keeps the chunking it was launched with)

@@ -30,6 +30,51 @@ GRID_BAD_POSE, GRID_CLIPPED = _lib.GRID_BAD_POSE, _lib.GRID_CLIPPED
 TILE = 64  # cells a side of the kernel's tile (lslam_grid.h GRID_T): the tests place rays on its seams
 
 
+def _stage_revolution(owner, xy, scan_chunk_off, chunk_pt_off, pose):
+    """The argument forms of ``OccupancyGrid.step`` -> device (xy, pt_off, pose).  ``owner`` holds ctx,
+    R and the staging buffers _xy, _off, _pose."""
+    R = owner.R
+    if isinstance(xy, MapInput):
+        xy, scan_chunk_off, chunk_pt_off = xy.xy, xy.sco, xy.cpo
+    if pose is None:
+        raise ValueError("pose is required (host [R, 3], a DeviceArray or a LandmarkMap)")
+    sco = np.ascontiguousarray(scan_chunk_off, np.int64).reshape(-1)
+    cpo = np.ascontiguousarray(chunk_pt_off, np.int64).reshape(-1)
+    if sco.size != R + 1:
+        raise ValueError("one revolution per robot: scan_chunk_off needs n_robots + 1 entries")
+    off = cpo[sco]
+    p0, p1 = int(off[0]), int(off[-1])
+    if p0 < 0 or np.any(np.diff(off) < 0) or p1 >= 2 ** 31:
+        raise ValueError("inconsistent CSR offsets")
+    if isinstance(xy, DeviceArray):
+        if xy.dtype != np.float64 or xy.nbytes < 16 * p1:
+            raise ValueError("device xy must be float64 [n, 2] with n >= the last point offset")
+        dxy = xy
+    else:
+        h = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
+        if h.shape[0] < p1:
+            raise ValueError("xy holds fewer points than chunk_pt_off describes")
+        dxy = owner._xy.put_host(h[p0:p1])
+        off = off - p0
+    if isinstance(pose, LandmarkMap):
+        if pose.R != R:
+            raise ValueError("the map holds %d robots, the grid %d" % (pose.R, R))
+        pose = pose.x
+    if isinstance(pose, DeviceArray):
+        if pose.dtype != np.float64 or pose.nbytes < 24 * R:
+            raise ValueError("device pose must be float64 [n_robots, 3]")
+        dpose = pose
+    else:
+        hp = np.ascontiguousarray(pose, np.float64)
+        if hp.size != 3 * R:
+            raise ValueError("pose must hold n_robots x 3 values")
+        dpose = owner._pose
+        dpose.upload_async(hp.reshape(R, 3))
+    owner._off.upload_async(np.ascontiguousarray(off, np.int32))
+    owner._off_host = np.ascontiguousarray(off, np.int64)
+    return dxy, owner._off, dpose
+
+
 class OccupancyGrid:
     """R robots' grids on one GPU.  ``params``: cell, max_range, grid_w, l_hit, l_miss, l_min, l_max
     (``lslam_grid_params``; defaults 20 mm, 8000 mm, 512, 85, -41, -200, 350; log-odds in 0.01 nat).
@@ -76,44 +121,7 @@ class OccupancyGrid:
         is ordered on the context's stream, before whatever overwrites them later.  ``pose``
         [R, 3] (x, y, theta): a host array, a float64 ``DeviceArray`` (``lm.x``) or a ``LandmarkMap``."""
         ctx, R = self.ctx, self.R
-        if isinstance(xy, MapInput):
-            xy, scan_chunk_off, chunk_pt_off = xy.xy, xy.sco, xy.cpo
-        if pose is None:
-            raise ValueError("pose is required (host [R, 3], a DeviceArray or a LandmarkMap)")
-        sco = np.ascontiguousarray(scan_chunk_off, np.int64).reshape(-1)
-        cpo = np.ascontiguousarray(chunk_pt_off, np.int64).reshape(-1)
-        if sco.size != R + 1:
-            raise ValueError("one revolution per robot: scan_chunk_off needs n_robots + 1 entries")
-        off = cpo[sco]
-        p0, p1 = int(off[0]), int(off[-1])
-        if p0 < 0 or np.any(np.diff(off) < 0) or p1 >= 2 ** 31:
-            raise ValueError("inconsistent CSR offsets")
-        if isinstance(xy, DeviceArray):
-            if xy.dtype != np.float64 or xy.nbytes < 16 * p1:
-                raise ValueError("device xy must be float64 [n, 2] with n >= the last point offset")
-            dxy = xy
-        else:
-            h = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
-            if h.shape[0] < p1:
-                raise ValueError("xy holds fewer points than chunk_pt_off describes")
-            dxy = self._xy.put_host(h[p0:p1])
-            off = off - p0
-        if isinstance(pose, LandmarkMap):
-            if pose.R != R:
-                raise ValueError("the map holds %d robots, the grid %d" % (pose.R, R))
-            pose = pose.x
-        if isinstance(pose, DeviceArray):
-            if pose.dtype != np.float64 or pose.nbytes < 24 * R:
-                raise ValueError("device pose must be float64 [n_robots, 3]")
-            dpose = pose
-        else:
-            hp = np.ascontiguousarray(pose, np.float64)
-            if hp.size != 3 * R:
-                raise ValueError("pose must hold n_robots x 3 values")
-            dpose = self._pose
-            dpose.upload_async(hp.reshape(R, 3))
-        doff = self._off
-        doff.upload_async(np.ascontiguousarray(off, np.int32))
+        dxy, doff, dpose = _stage_revolution(self, xy, scan_chunk_off, chunk_pt_off, pose)
         b = _lib.GridBatch()
         b.n_robots = R
         b.xy, b.pt_off, b.pose, b.origin = dxy.addr, doff.addr, dpose.addr, self.origin.addr
@@ -141,3 +149,102 @@ class OccupancyGrid:
     def upload(self, logodds):
         """Replace the grids (tests, restarts): int16 [R, W, W]."""
         self.logodds.upload(np.ascontiguousarray(logodds, np.int16).reshape(self.R, self.W, self.W))
+
+
+class GridRayCaster:
+    """Reads ``grid`` beam by beam (``lslam_grid_raycast``): every beam of a revolution is walked
+    from the pose through the robot's grid until the MAP says it stops (an occupied cell, an unknown
+    one, or the range circle), and classed by where it actually returned: MATCH, NOVEL (a return in
+    space the map holds free: a dynamic object), THROUGH (it passed a cell the map holds occupied:
+    a stale map or a wrong pose), UNMAPPED.  ``params``: occ_min, free_max, tol
+    (``lslam_raycast_params``; defaults 1, -1, 3 steps: L = 0 alone is unknown).  The grid's geometry and its device
+    buffers are ``grid``'s, read in place::
+
+        grid.step(xy, scan_chunk_off, chunk_pt_off, pose=lm)
+        rc.step(next_xy, scan_chunk_off, chunk_pt_off, pose=lm)   # before the next grid.step
+        if rc.inconsistency().max() > 0.3: ...                    # the pose contradicts the map
+
+    The definition is the comment on ``lslam_grid_raycast`` in include/lidarslam.h;
+    tests/raycast_ref.py is its NumPy form and the kernel matches it bit for bit, given ``rot``."""
+
+    def __init__(self, grid: OccupancyGrid, **params):
+        self.grid, self.ctx, self.R = grid, grid.ctx, grid.R
+        ctx, R = self.ctx, self.R
+        self.p = _lib.raycast_params(**params)
+        # (a range error of params surfaces here, before anything is allocated)
+        _lib.check(_lib.load().lslam_grid_raycast(ctx.handle, C.byref(_lib.RaycastBatch()), C.byref(grid.p),
+                                                  C.byref(self.p)), "lslam_grid_raycast")
+        self.counts = ctx.empty((R, 8), np.int32)
+        self.rot = ctx.empty((R, 2), np.float64)
+        self.flags = ctx.empty(R, np.int32)
+        for a in (self.counts, self.rot, self.flags):
+            a.fill_zero()
+        self._cls, self._stop = _Grow(ctx, np.uint8), _Grow(ctx, np.int32)
+        self._xy = _Grow(ctx, np.float64)
+        self._off = ctx.empty(R + 1, np.int32)
+        self._pose = ctx.empty((R, 3), np.float64)
+        self._off_host = np.zeros(R + 1, np.int64)
+        self.steps = 0
+
+    def step(self, xy, scan_chunk_off=None, chunk_pt_off=None, pose=None, sync=True, want_stop=True):
+        """One revolution per robot, in the argument forms of ``OccupancyGrid.step``; ``pose`` [R, 3]:
+        a host array, a float64 ``DeviceArray`` (``lm.x``) or a ``LandmarkMap``.  ``want_stop=False``
+        leaves the stop cells out (``stop`` NULL): classes and counts only."""
+        ctx, R, g = self.ctx, self.R, self.grid
+        dxy, doff, dpose = _stage_revolution(self, xy, scan_chunk_off, chunk_pt_off, pose)
+        P = int(self._off_host[-1])
+        b = _lib.RaycastBatch()
+        b.n_robots = R
+        b.xy, b.pt_off, b.pose, b.origin, b.logodds = dxy.addr, doff.addr, dpose.addr, g.origin.addr, g.logodds.addr
+        b.cls = self._cls.reserve(P).addr
+        b.stop = self._stop.reserve(3 * P).addr if want_stop else None
+        b.counts, b.rot, b.flags = self.counts.addr, self.rot.addr, self.flags.addr
+        _lib.check(_lib.load().lslam_grid_raycast(ctx.handle, C.byref(b), C.byref(g.p), C.byref(self.p)),
+                   "lslam_grid_raycast")
+        self._has_stop = bool(want_stop)
+        self.steps += 1
+        if sync:
+            ctx.sync()
+
+    def _head(self, grow, lo, hi, width=1):
+        """Items [lo, hi) x width of a grow-only buffer, on the host."""
+        out = np.empty((hi - lo) * width, grow.dtype)
+        if out.nbytes:
+            src = C.c_void_p(grow.buf.addr + lo * width * grow.dtype.itemsize)
+            _lib.check(self.ctx._L.lslam_d2h(self.ctx.handle, out.ctypes.data_as(C.c_void_p), src, out.nbytes),
+                       "lslam_d2h")
+        self.ctx.sync()
+        return out
+
+    def results(self):
+        """The last step's cls [P] (the class, 0..4), kind [P] (0 NONE, 1 UNKNOWN, 2 OCC), stop [P, 3]
+        (ox, oy, i_h; None without ``want_stop``), counts [R, 8], rot [R, 2], flags [R]; P points in
+        the order of the revolution, robot after robot."""
+        if not self.steps:
+            raise ValueError("no step yet")
+        lo, hi = int(self._off_host[0]), int(self._off_host[-1])
+        raw = self._head(self._cls, lo, hi)
+        stop = self._head(self._stop, lo, hi, 3).reshape(-1, 3) if self._has_stop else None
+        return {"cls": raw & 15, "kind": raw >> 4, "stop": stop, "counts": self.counts.download(),
+                "rot": self.rot.download(), "flags": self.flags.download()}
+
+    def expected_range(self):
+        """The range [P] (mm) at which the map expects every beam to return: cell * hypot(ox, oy) of the
+        stop cell where the kind is OCC, inf elsewhere.  On the host."""
+        r = self.results()
+        if r["stop"] is None:
+            raise ValueError("the last step left the stop cells out")
+        st = r["stop"].astype(np.float64)
+        return np.where(r["kind"] == _lib.RAYCAST_KIND_OCC, float(self.grid.p.cell) * np.hypot(st[:, 0], st[:, 1]), np.inf)
+
+    def novel_mask(self):
+        """bool [P]: the returns inside space the map holds free, the dynamic-object mask."""
+        lo, hi = int(self._off_host[0]), int(self._off_host[-1])
+        return (self._head(self._cls, lo, hi) & 15) == _lib.RAYCAST_NOVEL
+
+    def inconsistency(self):
+        """Per robot, (NOVEL + THROUGH) / valid points that are not beyond (0 where there are none): the
+        share of beams that contradict the map, the figure to gate a relocalisation on."""
+        c = self.counts.download().astype(np.int64)
+        den = c[:, 1:5].sum(1) - c[:, 5]
+        return np.where(den > 0, (c[:, _lib.RAYCAST_NOVEL] + c[:, _lib.RAYCAST_THROUGH]) / np.maximum(den, 1), 0.0)
