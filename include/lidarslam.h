@@ -476,6 +476,33 @@ typedef struct lslam_raycast_batch {
     int32_t *flags;           /* [n_robots] LSLAM_RAYCAST_* */
 } lslam_raycast_batch;
 
+/* ---- grid recentre flags (lslam_recentre_batch.flags) ---- */
+enum {
+    LSLAM_RECENTRE_BAD_POSE = 1,  /* as LSLAM_GRID_BAD_POSE, or a new origin that is not finite: nothing moves */
+    LSLAM_RECENTRE_MOVED = 2,     /* the grid and its origin were shifted by shift[r] cells */
+    LSLAM_RECENTRE_CLEARED = 4    /* with MOVED: the shift is a whole map or more on an axis, nothing was kept */
+};
+
+/* Grid recentre (lslam_grid_recentre), 16 bytes.  The grid's geometry comes from the lslam_grid_params
+ * given with the call. */
+typedef struct lslam_recentre_params {
+    int32_t margin;    /* cells: the robot cell may come this near an edge before the grid moves; 0..grid_w/2 (128) */
+    int32_t quantum;   /* cells: shifts are multiples of it; 1..64 (8: a moved row stays on the 16-byte groups
+                          that the readers load) */
+    int32_t reserved[2];
+} lslam_recentre_params;
+
+/* One recentre per robot, 48 bytes; all pointers DEVICE memory, all required. */
+typedef struct lslam_recentre_batch {
+    int32_t n_robots;
+    int32_t reserved;
+    const double *pose;       /* [n_robots][3] (x mm, y mm, theta rad), e.g. the filter's ukf_x */
+    double *origin;           /* [n_robots][2] in/out: world coordinates of the corner of cell (0, 0) */
+    int16_t *logodds;         /* [n_robots][grid_w][grid_w] in/out, row Y */
+    int32_t *shift;           /* [n_robots][2] (sx, sy) in cells: the grid now starts that many cells further on */
+    int32_t *flags;           /* [n_robots] LSLAM_RECENTRE_* */
+} lslam_recentre_batch;
+
 typedef struct lslam_ctx lslam_ctx;  /* opaque: device, stream, events, scratch */
 
 /* ---- library / context ---- */
@@ -520,6 +547,8 @@ int lslam_mapfuse_abi_sizes(int64_t *sizes, int n);
 int lslam_reloc_abi_sizes(int64_t *sizes, int n);
 /* and for lslam_raycast_params, lslam_raycast_batch.  Writes min(n, 2) entries, returns 2. */
 int lslam_raycast_abi_sizes(int64_t *sizes, int n);
+/* and for lslam_recentre_params, lslam_recentre_batch.  Writes min(n, 2) entries, returns 2. */
+int lslam_recentre_abi_sizes(int64_t *sizes, int n);
 /* per-kernel HIP-event timing on the ctx stream (kernel ids: LSLAM_K_*) */
 enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMARK = 3, LSLAM_K_UKF = 4,
        LSLAM_K_RNG = 5 /* parity-stream producer */, LSLAM_K_CONSENSUS = 6 /* per-chunk A4-A8 */,
@@ -528,7 +557,7 @@ enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMAR
        LSLAM_K_MATCH = 9 /* a whole scan-match call */, LSLAM_K_GRID = 10 /* a whole grid update */,
        LSLAM_K_MAPMATCH = 11 /* a whole scan-to-map call */, LSLAM_K_MAPFUSE = 12 /* a whole match-fusion call */,
        LSLAM_K_RELOC = 13 /* a whole relocalisation call */, LSLAM_K_RAYCAST = 14 /* a whole grid ray-cast call */,
-       LSLAM_K_COUNT = 15 };
+       LSLAM_K_RECENTRE = 15 /* a whole grid recentre call */, LSLAM_K_COUNT = 16 };
 int lslam_set_timing(lslam_ctx *ctx, int enable);
 /* which kernel ids are timed while timing is on (bit k = LSLAM_K_k; default all).  Timing
  * events between the producer and consumer kernels change how the two streams overlap,
@@ -556,6 +585,7 @@ int lslam_mapmatch_params_default(lslam_mapmatch_params *p);
 int lslam_mapfuse_params_default(lslam_mapfuse_params *p);
 int lslam_reloc_params_default(lslam_reloc_params *p);
 int lslam_raycast_params_default(lslam_raycast_params *p);
+int lslam_recentre_params_default(lslam_recentre_params *p);
 /* smallest e with RN(sqrt(e)) >= thr: (residual < thr) <=> (squared residual < cutoff) */
 double lslam_inlier_cutoff(double thr);
 /* MerweScaledSigmaPoints weights (filterpy _compute_weights) for n = 3 */
@@ -837,6 +867,38 @@ int lslam_map_relocalize(lslam_ctx *ctx, const lslam_reloc_batch *b, const lslam
  * touched; n_robots == 0 does nothing. */
 int lslam_grid_raycast(lslam_ctx *ctx, const lslam_raycast_batch *b, const lslam_grid_params *g,
                        const lslam_raycast_params *p);
+
+/* Grid recentre: the rolling map.  Each robot's grid and its origin are shifted by whole cells, in
+ * place, so that the robot's cell comes back to the middle; what scrolls off is lost (there is no
+ * archive of the strip that leaves) and what scrolls in is unknown.  Every reader of the grid takes
+ * origin as a device pointer and follows.  The grid's geometry is g's cell and grid_w (g is checked as
+ * lslam_grid_update checks it), W = grid_w, inv = 1.0 / cell; margin <= W / 2.  Per robot r, in FP64
+ * with every operation rounded on its own, then integers:
+ *   0. robot cell and bad poses: X0d = floor((px - ox) inv), Y0d = floor((py - oy) inv), and the
+ *      condition of a bad pose, are step 0 of lslam_grid_update (a non-finite pose component or
+ *      origin, or |X0d| or |Y0d| >= 2^20).  A bad pose leaves grid and origin untouched:
+ *      shift[r] = (0, 0), flags[r] = LSLAM_RECENTRE_BAD_POSE.  Otherwise (X0, Y0) are the integers.
+ *   1. the shift.  If margin <= X0 < W - margin and margin <= Y0 < W - margin: (sx, sy) = (0, 0).
+ *      Otherwise both axes are recentred: s = quantum floordiv(c - W div 2 + quantum div 2, quantum)
+ *      for c = X0, Y0, where floordiv rounds toward minus infinity and the halves are integer halves.
+ *   2. a shift of (0, 0), also one that step 1 triggered and rounded to zero, writes shift[r] = (0, 0)
+ *      and flags[r] = 0 and nothing else: logodds and origin keep every bit.
+ *   3. the new origin, per axis: origin' = fl(origin + fl(s cell)), two roundings, no fused
+ *      multiply-add.  If origin' is not finite the robot is a bad pose as in step 0.
+ *   4. the new grid: L'[y][x] = L[y + sy][x + sx] where that source cell is on the map, 0 (unknown)
+ *      elsewhere.  Cells move as 16-bit patterns: nothing is clamped, values outside [l_min, l_max]
+ *      survive.  flags[r] = LSLAM_RECENTRE_MOVED, and | LSLAM_RECENTRE_CLEARED when |sx| >= W or
+ *      |sy| >= W (nothing is kept).
+ *   5. shift[r] = (sx, sy); origin[r] = origin'; logodds in place.
+ * The world square of a cell that stays on the map is the same before and after, up to the two
+ * roundings of step 3 (none when origin is a multiple of cell that FP64 holds exactly).
+ * Runs on the context's main stream, after every earlier call and before every later one: it sees the
+ * ukf_x of a preceding lslam_scan_pipeline, and a following lslam_grid_update, lslam_map_match,
+ * lslam_map_fuse, lslam_map_relocalize or lslam_grid_raycast sees the moved grid and origin.
+ * Out-of-range parameters and missing pointers return LSLAM_ERR_ARG (the message names the field),
+ * checked before the context is touched; n_robots == 0 does nothing. */
+int lslam_grid_recentre(lslam_ctx *ctx, const lslam_recentre_batch *b, const lslam_grid_params *g,
+                        const lslam_recentre_params *p);
 
 #ifdef __cplusplus
 }

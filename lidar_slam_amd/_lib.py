@@ -30,7 +30,7 @@ HYP_MT19937, HYP_PHILOX, HYP_EXPLICIT = 0, 1, 2
 UKF_PREDICT, UKF_UPDATE, UKF_LMK_FROM_RANSAC, UKF_MAP, UKF_SIGMAS_IN = 1, 2, 4, 8, 16
 K_POLAR, K_HYP, K_PIPELINE, K_LANDMARK, K_UKF, K_RNG, K_CONSENSUS = 0, 1, 2, 3, 4, 5, 6
 K_EXPRESS, K_EXPRESS_SCATTER, K_MATCH, K_GRID, K_MAPMATCH, K_MAPFUSE, K_RELOC = 7, 8, 9, 10, 11, 12, 13
-K_RAYCAST = 14
+K_RAYCAST, K_RECENTRE = 14, 15
 MATCH_EMPTY, MATCH_EDGE = 1, 2
 GRID_BAD_POSE, GRID_CLIPPED = 1, 2
 MAPMATCH_EMPTY, MAPMATCH_EDGE, MAPMATCH_BAD_POSE, MAPMATCH_WEAK = 1, 2, 4, 8
@@ -39,6 +39,7 @@ RELOC_LOST, RELOC_AMBIGUOUS = 1, 2
 RAYCAST_BAD_POSE = 1
 RAYCAST_INVALID, RAYCAST_MATCH, RAYCAST_NOVEL, RAYCAST_THROUGH, RAYCAST_UNMAPPED = 0, 1, 2, 3, 4  # cls & 15
 RAYCAST_KIND_NONE, RAYCAST_KIND_UNKNOWN, RAYCAST_KIND_OCC = 0, 1, 2  # cls >> 4
+RECENTRE_BAD_POSE, RECENTRE_MOVED, RECENTRE_CLEARED = 1, 2, 4
 
 
 class HIPLibraryError(RuntimeError):
@@ -152,6 +153,15 @@ class RaycastBatch(C.Structure):
                [(n, _VP) for n in ("xy", "pt_off", "pose", "origin", "logodds", "cls", "stop", "counts", "rot", "flags")]
 
 
+class RecentreParams(C.Structure):
+    _fields_ = [("margin", C.c_int32), ("quantum", C.c_int32), ("reserved", C.c_int32 * 2)]
+
+
+class RecentreBatch(C.Structure):
+    _fields_ = [("n_robots", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, _VP) for n in ("pose", "origin", "logodds", "shift", "flags")]
+
+
 assert C.sizeof(ChunkModel) == 112
 assert C.sizeof(LandmarkRec) == 56
 
@@ -170,6 +180,7 @@ EXPORTS = [
     "lslam_mapfuse_abi_sizes", "lslam_mapfuse_params_default", "lslam_map_fuse",
     "lslam_reloc_abi_sizes", "lslam_reloc_params_default", "lslam_map_relocalize", "lslam_set_reloc_budget",
     "lslam_raycast_abi_sizes", "lslam_raycast_params_default", "lslam_grid_raycast",
+    "lslam_recentre_abi_sizes", "lslam_recentre_params_default", "lslam_grid_recentre",
 ]
 
 _lib = None
@@ -251,6 +262,9 @@ def load():
         "lslam_raycast_abi_sizes": ([P(i64), C.c_int], C.c_int),
         "lslam_raycast_params_default": ([P(RaycastParams)], C.c_int),
         "lslam_grid_raycast": ([_VP, P(RaycastBatch), P(GridParams), P(RaycastParams)], C.c_int),
+        "lslam_recentre_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_recentre_params_default": ([P(RecentreParams)], C.c_int),
+        "lslam_grid_recentre": ([_VP, P(RecentreBatch), P(GridParams), P(RecentreParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -291,10 +305,12 @@ def _check_abi(L):
     L.lslam_reloc_abi_sizes(got5, 2)
     got6 = (C.c_int64 * 2)()
     L.lslam_raycast_abi_sizes(got6, 2)
-    got = list(got) + list(got2) + list(got3) + list(got4) + list(got5) + list(got6)
+    got7 = (C.c_int64 * 2)()
+    L.lslam_recentre_abi_sizes(got7, 2)
+    got = list(got) + list(got2) + list(got3) + list(got4) + list(got5) + list(got6) + list(got7)
     want = want + [C.sizeof(GridParams), C.sizeof(GridBatch), C.sizeof(MapMatchParams), C.sizeof(MapMatchBatch),
                    C.sizeof(MapFuseParams), C.sizeof(MapFuseBatch), C.sizeof(RelocParams), C.sizeof(RelocBatch),
-                   C.sizeof(RaycastParams), C.sizeof(RaycastBatch)]
+                   C.sizeof(RaycastParams), C.sizeof(RaycastBatch), C.sizeof(RecentreParams), C.sizeof(RecentreBatch)]
     if list(got) != want:
         _err = HIPLibraryError("struct sizes differ between %s %s and the ctypes layouts %s"
                                % (LIB_PATH, list(got), want))
@@ -391,6 +407,14 @@ def reloc_params(**kw):
 def raycast_params(**kw):
     p = RaycastParams()
     load().lslam_raycast_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def recentre_params(**kw):
+    p = RecentreParams()
+    load().lslam_recentre_params_default(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -10,7 +10,8 @@
 //   (the occupancy-grid kernel; its integer ray is lslam_grid_ray.h, plain C++), lslam_mapmatch.h
 //   (the scan-to-map matcher's two kernels), lslam_mapfuse.h (the match-fusion kernel),
 //   lslam_reloc.h (the relocalisation kernels), lslam_raycast.h (the grid ray-cast kernel; one
-//   beam's walk is lslam_raycast_walk.h, plain C++);
+//   beam's walk is lslam_raycast_walk.h, plain C++), lslam_recentre.h (the grid recentre kernel; its
+//   shift rule and in-place plan are lslam_recentre_plan.h, plain C++);
 // the host side is included at the foot:
 //   lslam_hazards.h  which waits a call's producer needs (plain C++, no HIP)
 //   lslam_ctx.h      lslam_ctx, its grow-only device buffers and timers, create / destroy,
@@ -3060,6 +3061,8 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
 #include "lslam_reloc.h"
 // the grid ray-cast kernel, last: the walk of lslam_raycast_walk.h through a window of the grid
 #include "lslam_raycast.h"
+// the grid recentre kernel: the one writer of origin, and the second of logodds
+#include "lslam_recentre.h"
 
 // ------------------------------------------------------------------------
 // host side: the context, then the launchers and entry points

@@ -403,6 +403,12 @@ int lslam_raycast_abi_sizes(int64_t *sizes, int n) {
     return 2;
 }
 
+int lslam_recentre_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[2] = {(int64_t)sizeof(lslam_recentre_params), (int64_t)sizeof(lslam_recentre_batch)};
+    for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
+    return 2;
+}
+
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
     if (!c || (!dst && n)) return LSLAM_ERR_ARG;
     if (!n) return LSLAM_OK;
@@ -578,6 +584,14 @@ int lslam_raycast_params_default(lslam_raycast_params *p) {
     p->occ_min = 1;
     p->free_max = -1;
     p->tol = 3;         // steps: the map's walls are one to two cells thick
+    return LSLAM_OK;
+}
+
+int lslam_recentre_params_default(lslam_recentre_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->margin = 128;  // cells: a quarter of the default map; the grid moves before max_range reaches far past the edge
+    p->quantum = 8;   // cells: 16 bytes of a row, the group every reader of the grid loads
     return LSLAM_OK;
 }
 

@@ -1235,6 +1235,48 @@ static int launch_raycast(lslam_ctx *c, const lslam_raycast_batch *b, const lsla
     return LSLAM_OK;
 }
 
+// ---- grid recentre (lslam_recentre.h) ----
+
+static int recentre_check_params(const lslam_recentre_params *p, const lslam_grid_params *g) {
+    if (!p) return set_err(LSLAM_ERR_ARG, "recentre: params is NULL");
+    if (p->margin < 0 || p->margin > g->grid_w / 2)
+        return set_err(LSLAM_ERR_ARG, "recentre: margin must be in [0, grid_w / 2]");
+    if (p->quantum < 1 || p->quantum > 64) return set_err(LSLAM_ERR_ARG, "recentre: quantum must be in [1, 64]");
+    return LSLAM_OK;
+}
+
+// One workgroup per robot (two on one robot would race: lslam_recentre.h).  With grid_w and quantum
+// multiples of 8 every shift lies on 16-byte groups and the instantiation without the lane-per-cell
+// path, and without its LDS, is launched.
+static int launch_recentre(lslam_ctx *c, const lslam_recentre_batch *b, const lslam_grid_params *g,
+                           const lslam_recentre_params *p) {
+    RecentreArgs k;
+    memset(&k, 0, sizeof(k));
+    k.b = *b;
+    k.cell = g->cell;
+    k.inv = 1.0 / g->cell;
+    k.grid_w = g->grid_w;
+    k.margin = p->margin;
+    k.quantum = p->quantum;
+    k.band_rows = recentre_band_rows(g->grid_w);
+    k.vec = (g->grid_w % 8 == 0 && ((uintptr_t)b->logodds & 15) == 0) ? 1 : 0;
+    if (b->n_robots > (1 << 30)) return set_err(LSLAM_ERR_UNSUPPORTED, "recentre: too many robots in one call");
+    int st = timer_begin(c, LSLAM_K_RECENTRE);
+    if (st) return st;
+    if (k.vec && p->quantum % 8 == 0)
+        hipLaunchKernelGGL(recentre_kernel<0>, dim3((unsigned)recentre_blocks(b->n_robots)), dim3(RECENTRE_TPB), 0, c->stream, k);
+    else
+        hipLaunchKernelGGL(recentre_kernel<1>, dim3((unsigned)recentre_blocks(b->n_robots)), dim3(RECENTRE_TPB), 0, c->stream, k);
+    HIPCHK(hipGetLastError());
+    if ((st = timer_end(c, LSLAM_K_RECENTRE))) return st;
+    const size_t R = (size_t)b->n_robots;
+    c->hz.outs.add(b->logodds, R * (size_t)g->grid_w * (size_t)g->grid_w * 2);
+    c->hz.outs.add(b->origin, R * 16);
+    c->hz.outs.add(b->shift, R * 8);
+    c->hz.outs.add(b->flags, R * 4);
+    return LSLAM_OK;
+}
+
 // ---- express-scan codec (lslam_express.h) ----
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1518,6 +1560,26 @@ int lslam_grid_raycast(lslam_ctx *c, const lslam_raycast_batch *b, const lslam_g
     if (b->n_robots == 0) return LSLAM_OK;
     HIPCHK(hipSetDevice(c->device));
     return launch_raycast(c, b, g, p);
+}
+
+// On the main stream, as lslam_grid_update: ordered after the calls that read the grid where it was and
+// before the calls that read it where it is.
+int lslam_grid_recentre(lslam_ctx *c, const lslam_recentre_batch *b, const lslam_grid_params *g,
+                        const lslam_recentre_params *p) {
+    int st = grid_check_params(g);
+    if (st) return st;
+    if ((st = recentre_check_params(p, g))) return st;
+    if (!b) return set_err(LSLAM_ERR_ARG, "recentre: batch is NULL");
+    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "recentre: negative n_robots");
+    if (b->n_robots > 0) {
+        if (!b->pose || !b->origin || !b->logodds)
+            return set_err(LSLAM_ERR_ARG, "recentre: missing input (pose, origin, logodds)");
+        if (!b->shift || !b->flags) return set_err(LSLAM_ERR_ARG, "recentre: missing output (shift, flags)");
+    }
+    if (!c) return set_err(LSLAM_ERR_ARG, "recentre: ctx is NULL");
+    if (b->n_robots == 0) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return launch_recentre(c, b, g, p);
 }
 
 // (the scratch is sized per call: a call in flight keeps the chunking it was launched with)

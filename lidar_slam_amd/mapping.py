@@ -9,6 +9,7 @@ the cells it crosses become freer, the cell it ends in more occupied.  It chains
 
     odo.step(xy, scan_chunk_off, chunk_pt_off, lm)       # writes lm.u
     lm.step(xy, scan_chunk_off, chunk_pt_off)            # writes lm.x
+    grid.recentre(pose=lm)                               # rolls the grid under a robot that nears its edge
     grid.step(xy, scan_chunk_off, chunk_pt_off, pose=lm)  # reads lm.x and the points in place
 
 The definition (robot cell, integer ray, per-revolution sum, one clamp per call) is the comment on
@@ -27,7 +28,34 @@ from .odometry import _Grow
 from .slam import LandmarkMap, MapInput
 
 GRID_BAD_POSE, GRID_CLIPPED = _lib.GRID_BAD_POSE, _lib.GRID_CLIPPED
+RECENTRE_BAD_POSE, RECENTRE_MOVED, RECENTRE_CLEARED = _lib.RECENTRE_BAD_POSE, _lib.RECENTRE_MOVED, _lib.RECENTRE_CLEARED
 TILE = 64  # cells a side of the kernel's tile (lslam_grid.h GRID_T): the tests place rays on its seams
+
+
+def recentre_band_rows(grid_w):
+    """Rows of a band of the recentre kernel (lslam_recentre_plan.h recentre_band_rows): as many whole
+    rows as 16384 cells hold.  The tests place shifts on its seams."""
+    return max(1, min(int(grid_w), 16384 // int(grid_w)))
+
+
+def _stage_pose(owner, pose):
+    """The pose forms of ``OccupancyGrid.step`` -> a device [R, 3] float64."""
+    R = owner.R
+    if pose is None:
+        raise ValueError("pose is required (host [R, 3], a DeviceArray or a LandmarkMap)")
+    if isinstance(pose, LandmarkMap):
+        if pose.R != R:
+            raise ValueError("the map holds %d robots, the grid %d" % (pose.R, R))
+        pose = pose.x
+    if isinstance(pose, DeviceArray):
+        if pose.dtype != np.float64 or pose.nbytes < 24 * R:
+            raise ValueError("device pose must be float64 [n_robots, 3]")
+        return pose
+    hp = np.ascontiguousarray(pose, np.float64)
+    if hp.size != 3 * R:
+        raise ValueError("pose must hold n_robots x 3 values")
+    owner._pose.upload_async(hp.reshape(R, 3))
+    return owner._pose
 
 
 def _stage_revolution(owner, xy, scan_chunk_off, chunk_pt_off, pose):
@@ -56,20 +84,7 @@ def _stage_revolution(owner, xy, scan_chunk_off, chunk_pt_off, pose):
             raise ValueError("xy holds fewer points than chunk_pt_off describes")
         dxy = owner._xy.put_host(h[p0:p1])
         off = off - p0
-    if isinstance(pose, LandmarkMap):
-        if pose.R != R:
-            raise ValueError("the map holds %d robots, the grid %d" % (pose.R, R))
-        pose = pose.x
-    if isinstance(pose, DeviceArray):
-        if pose.dtype != np.float64 or pose.nbytes < 24 * R:
-            raise ValueError("device pose must be float64 [n_robots, 3]")
-        dpose = pose
-    else:
-        hp = np.ascontiguousarray(pose, np.float64)
-        if hp.size != 3 * R:
-            raise ValueError("pose must hold n_robots x 3 values")
-        dpose = owner._pose
-        dpose.upload_async(hp.reshape(R, 3))
+    dpose = _stage_pose(owner, pose)
     owner._off.upload_async(np.ascontiguousarray(off, np.int32))
     owner._off_host = np.ascontiguousarray(off, np.int64)
     return dxy, owner._off, dpose
@@ -79,7 +94,8 @@ class OccupancyGrid:
     """R robots' grids on one GPU.  ``params``: cell, max_range, grid_w, l_hit, l_miss, l_min, l_max
     (``lslam_grid_params``; defaults 20 mm, 8000 mm, 512, 85, -41, -200, 350; log-odds in 0.01 nat).
     ``origin`` [R, 2] (or one pair for all): the world coordinates of the corner of cell (0, 0);
-    default: every grid centred on (0, 0)."""
+    default: every grid centred on (0, 0).  ``recentre`` moves it, on the device; ``origin_host`` is
+    the host's copy, refreshed on its next read after a ``recentre``."""
 
     def __init__(self, ctx: Context, n_robots: int, origin=None, **params):
         R = int(n_robots)
@@ -90,11 +106,12 @@ class OccupancyGrid:
         self.W = int(self.p.grid_w)
         half = 0.5 * self.W * self.p.cell
         o = np.full((R, 2), -half) if origin is None else np.asarray(origin, np.float64)
-        self.origin_host = np.ascontiguousarray(np.broadcast_to(o, (R, 2)), np.float64)
+        self._origin_host = np.ascontiguousarray(np.broadcast_to(o, (R, 2)), np.float64)
+        self._origin_stale = False  # a recentre may have moved the device's origin since the last read
         # (a range error of params surfaces here, from the first call, before anything large is allocated)
         _lib.check(_lib.load().lslam_grid_update(ctx.handle, C.byref(_lib.GridBatch()), C.byref(self.p)),
                    "lslam_grid_update")
-        self.origin = ctx.to_device(self.origin_host)
+        self.origin = ctx.to_device(self._origin_host)
         self.logodds = ctx.empty((R, self.W, self.W), np.int16)
         self.logodds.fill_zero()
         self.rot = ctx.empty((R, 2), np.float64)
@@ -106,6 +123,16 @@ class OccupancyGrid:
         self._off = ctx.empty(R + 1, np.int32)  # (uploads are ordered on the stream: a step in flight keeps its own)
         self._pose = ctx.empty((R, 3), np.float64)
         self.steps = 0
+        self._shift = self._rflags = None  # recentre's outputs, allocated by its first call
+
+    @property
+    def origin_host(self):
+        """origin [R, 2] on the host.  After a ``recentre`` the next read waits for the stream and
+        downloads the 16 bytes per robot; without one it is the array given at construction."""
+        if self._origin_stale:
+            self._origin_host = self.origin.download()
+            self._origin_stale = False
+        return self._origin_host
 
     @classmethod
     def centred_on(cls, ctx, x0, **params):
@@ -130,6 +157,36 @@ class OccupancyGrid:
         self.steps += 1
         if sync:
             ctx.sync()
+
+    def recentre(self, pose, margin=None, quantum=None, sync=True):
+        """Roll every grid whose robot is within ``margin`` cells of an edge (``lslam_grid_recentre``):
+        the grid and ``origin`` move by whole cells, multiples of ``quantum``, in place on the device,
+        so that the robot's cell is back in the middle.  What scrolls off is lost; what scrolls in is
+        unknown.  ``pose`` as in ``step``; ``margin``, ``quantum``: ``lslam_recentre_params`` (defaults
+        128 and 8 cells).  The localizers and ray casters built on this grid read ``origin`` on the
+        device and follow."""
+        ctx, R = self.ctx, self.R
+        kw = {k: int(v) for k, v in (("margin", margin), ("quantum", quantum)) if v is not None}
+        q = _lib.recentre_params(**kw)
+        dpose = _stage_pose(self, pose)
+        if self._shift is None:
+            self._shift, self._rflags = ctx.empty((R, 2), np.int32), ctx.empty(R, np.int32)
+        b = _lib.RecentreBatch()
+        b.n_robots = R
+        b.pose, b.origin, b.logodds = dpose.addr, self.origin.addr, self.logodds.addr
+        b.shift, b.flags = self._shift.addr, self._rflags.addr
+        _lib.check(_lib.load().lslam_grid_recentre(ctx.handle, C.byref(b), C.byref(self.p), C.byref(q)),
+                   "lslam_grid_recentre")
+        self._origin_stale = True
+        if sync:
+            ctx.sync()
+
+    def recentre_results(self):
+        """The last ``recentre``'s shift [R, 2] (sx, sy in cells), flags [R] (RECENTRE_*) and the origin
+        [R, 2] as it now stands."""
+        if self._shift is None:
+            raise ValueError("no recentre yet")
+        return {"shift": self._shift.download(), "flags": self._rflags.download(), "origin": self.origin_host}
 
     def results(self):
         """logodds [R, W, W] int16 (row Y, 0.01 nat) and the last step's rot [R, 2], n_used [R, 2]
