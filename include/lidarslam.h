@@ -503,6 +503,66 @@ typedef struct lslam_recentre_batch {
     int32_t *flags;           /* [n_robots] LSLAM_RECENTRE_* */
 } lslam_recentre_batch;
 
+/* ---- distance-field modes (lslam_dist_params.mode) and flags (lslam_dist_batch.flags) ---- */
+enum {
+    LSLAM_DIST_OCC = 0,       /* the sources are the occupied cells: L >= occ_min */
+    LSLAM_DIST_NOT_FREE = 1   /* the sources are the cells that are not free, L > free_max, and every cell off the map */
+};
+enum {
+    LSLAM_DIST_EMPTY = 1      /* no source cell on the map */
+};
+
+/* Distance field (lslam_grid_distance), 16 bytes.  The grid's geometry is the grid_w of the
+ * lslam_grid_params given with the call. */
+typedef struct lslam_dist_params {
+    int32_t mode;      /* LSLAM_DIST_OCC (0) or LSLAM_DIST_NOT_FREE */
+    int32_t occ_min;   /* OCC: a cell is a source iff L >= occ_min; -32768..32767 (85, the matchers' threshold) */
+    int32_t free_max;  /* NOT_FREE: a cell is a source iff L > free_max; -32768..32767 (-1, the ray caster's) */
+    int32_t d_max;     /* cells, 1..255 (64): the field saturates at d_max^2 */
+} lslam_dist_params;
+
+/* One field per robot, 40 bytes; all pointers DEVICE memory, all required. */
+typedef struct lslam_dist_batch {
+    int32_t n_robots;
+    int32_t reserved;
+    const int16_t *logodds;   /* [n_robots][grid_w][grid_w], row Y: read only */
+    uint16_t *d2;             /* [n_robots][grid_w][grid_w] out: min(squared distance in cells, d_max^2) */
+    int32_t *n_src;           /* [n_robots] source cells on the map */
+    int32_t *flags;           /* [n_robots] LSLAM_DIST_* */
+} lslam_dist_batch;
+
+/* ---- field-score flags (lslam_fieldscore_batch.flags) ---- */
+enum {
+    LSLAM_FIELD_BAD_POSE = 1  /* as LSLAM_GRID_BAD_POSE: nothing is scored */
+};
+
+/* The field read under a revolution (lslam_field_score), 16 bytes.  v is the field's value at a
+ * point's hit cell. */
+typedef struct lslam_fieldscore_params {
+    int32_t trunc2;    /* a point adds min(v, trunc2); 1..65025 (625: 25 cells, an outlier costs no more) */
+    int32_t near2;     /* a point is near iff v <= near2; 0..65025 (4) */
+    int32_t off2;      /* v of a hit cell (or robot cell) off the map; 0..65025 (4096, the default d_max squared) */
+    int32_t reserved;
+} lslam_fieldscore_params;
+
+/* One revolution per robot scored in the robot's field, 80 bytes; all pointers DEVICE memory, all
+ * required.  P = pt_off[n_robots]. */
+typedef struct lslam_fieldscore_batch {
+    int32_t n_robots;
+    int32_t reserved;
+    /* inputs */
+    const double *xy;         /* [P][2] revolutions, each in its robot's frame */
+    const int32_t *pt_off;    /* [n_robots+1] CSR robot -> points */
+    const double *pose;       /* [n_robots][3] (x mm, y mm, theta rad), e.g. the filter's ukf_x */
+    const double *origin;     /* [n_robots][2] world coordinates of the corner of cell (0, 0) */
+    const uint16_t *d2;       /* [n_robots][grid_w][grid_w] the field of lslam_grid_distance: read only */
+    /* outputs */
+    double *rot;              /* [n_robots][2] (cos theta, sin theta) as used */
+    int64_t *stats;           /* [n_robots][4] (sum of min(v, trunc2), points scored, near points, points off the map) */
+    int32_t *clear2;          /* [n_robots] d2 at the robot cell (off2 if it is off the map) */
+    int32_t *flags;           /* [n_robots] LSLAM_FIELD_* */
+} lslam_fieldscore_batch;
+
 typedef struct lslam_ctx lslam_ctx;  /* opaque: device, stream, events, scratch */
 
 /* ---- library / context ---- */
@@ -549,6 +609,9 @@ int lslam_reloc_abi_sizes(int64_t *sizes, int n);
 int lslam_raycast_abi_sizes(int64_t *sizes, int n);
 /* and for lslam_recentre_params, lslam_recentre_batch.  Writes min(n, 2) entries, returns 2. */
 int lslam_recentre_abi_sizes(int64_t *sizes, int n);
+/* and for lslam_dist_params, lslam_dist_batch, lslam_fieldscore_params, lslam_fieldscore_batch.
+ * Writes min(n, 4) entries, returns 4. */
+int lslam_dist_abi_sizes(int64_t *sizes, int n);
 /* per-kernel HIP-event timing on the ctx stream (kernel ids: LSLAM_K_*) */
 enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMARK = 3, LSLAM_K_UKF = 4,
        LSLAM_K_RNG = 5 /* parity-stream producer */, LSLAM_K_CONSENSUS = 6 /* per-chunk A4-A8 */,
@@ -586,6 +649,8 @@ int lslam_mapfuse_params_default(lslam_mapfuse_params *p);
 int lslam_reloc_params_default(lslam_reloc_params *p);
 int lslam_raycast_params_default(lslam_raycast_params *p);
 int lslam_recentre_params_default(lslam_recentre_params *p);
+int lslam_dist_params_default(lslam_dist_params *p);
+int lslam_fieldscore_params_default(lslam_fieldscore_params *p);
 /* smallest e with RN(sqrt(e)) >= thr: (residual < thr) <=> (squared residual < cutoff) */
 double lslam_inlier_cutoff(double thr);
 /* MerweScaledSigmaPoints weights (filterpy _compute_weights) for n = 3 */
@@ -899,6 +964,53 @@ int lslam_grid_raycast(lslam_ctx *ctx, const lslam_raycast_batch *b, const lslam
  * checked before the context is touched; n_robots == 0 does nothing. */
 int lslam_grid_recentre(lslam_ctx *ctx, const lslam_recentre_batch *b, const lslam_grid_params *g,
                         const lslam_recentre_params *p);
+
+/* Distance field: for every cell of every robot's grid, the squared Euclidean distance, in cells, to
+ * the nearest source cell, saturated: the clearance of a planner, the likelihood field of a scorer.
+ * The grid's geometry is g's grid_w alone, W = grid_w (g is checked as lslam_grid_update checks it).
+ * All integers; cap = d_max d_max.  Per robot r:
+ *   0. sources.  LSLAM_DIST_OCC: cell (x, y) is a source iff L[y][x] >= occ_min.  LSLAM_DIST_NOT_FREE:
+ *      iff L[y][x] > free_max, and every cell off the map is a source too (unknown space is an
+ *      obstacle to a planner).  L is read as the 16-bit value it holds, clamped or not.
+ *   1. d2[y][x] = min(cap, min over source cells (x', y') of (x - x')^2 + (y - y')^2).  A source cell
+ *      has d2 = 0.  The sources off the map of NOT_FREE amount to the minimum with b b,
+ *      b = min(x + 1, W - x, y + 1, W - y).
+ *   2. n_src[r] = the source cells on the map; flags[r] = LSLAM_DIST_EMPTY iff n_src[r] = 0, else 0.
+ *      An EMPTY map gives cap everywhere in OCC mode and min(cap, b b) in NOT_FREE mode.
+ * Every cell of d2 is written on every call; logodds is read only.  d2 must not overlap logodds
+ * (LSLAM_ERR_ARG).  The field is recomputed whole: there is no incremental update after a revolution.
+ * The transform is separable (a column pass g[y][x] = distance to the nearest source of column x
+ * saturated at d_max, then d2[y][x] = min over |x - x'| < d_max of (x - x')^2 + g[y][x']^2); the
+ * result is integers, so every correct form gives these bits.  The kernel keeps g in LDS
+ * (lslam_dist.h); a grid_w above 1757 with a d_max its bitmap cannot hold (grid_w 2048: above 205)
+ * returns LSLAM_ERR_UNSUPPORTED.
+ * Runs on the context's main stream, after every earlier call: it sees the grid of a preceding
+ * lslam_grid_update or lslam_grid_recentre.  Out-of-range parameters and missing pointers return
+ * LSLAM_ERR_ARG (the message names the field), checked before the context is touched;
+ * n_robots == 0 does nothing. */
+int lslam_grid_distance(lslam_ctx *ctx, const lslam_dist_batch *b, const lslam_grid_params *g,
+                        const lslam_dist_params *p);
+
+/* The field read under a revolution: one revolution per robot, the robot's pose and its distance
+ * field -> how far the revolution's returns lie from the map's sources, and the robot's own
+ * clearance.  The grid's geometry is g's cell, grid_w and max_range.  Per robot r:
+ *   0. pose, rotation and robot cell: step 0 of lslam_grid_update, verbatim; (c, s) go to rot[r]
+ *      (always) and the written bits are the definition's input.  A bad pose (that step's condition)
+ *      gives flags[r] = LSLAM_FIELD_BAD_POSE, stats[r] all zero and clear2[r] = 0.  Otherwise
+ *      flags[r] = 0 and clear2[r] = d2[Y0][X0], or off2 if the robot cell (X0, Y0) is off the map.
+ *   1. points: step 1 of lslam_grid_update, verbatim: a valid point (both coordinates finite, not
+ *      exactly (0, 0)) that is not beyond (x x + y y > max_range max_range) has the hit cell (X1, Y1).
+ *      v = d2[Y1][X1] on the map, off2 off it.
+ *   2. stats[r] = (sum of min(v, trunc2), points scored, points with v <= near2, points whose hit
+ *      cell is off the map), over those points: integers, so the order of accumulation does not
+ *      matter.
+ * cell sqrt(clear2) is the robot's clearance; stats[2] / stats[1] the share of returns on the map's
+ * sources; stats[0] / stats[1] the mean truncated squared distance, the beam-end-point score.
+ * pose may alias the filter's ukf_x.  Runs on the context's main stream, after every earlier call.
+ * Out-of-range parameters and missing pointers return LSLAM_ERR_ARG (the message names the field),
+ * checked before the context is touched; n_robots == 0 does nothing. */
+int lslam_field_score(lslam_ctx *ctx, const lslam_fieldscore_batch *b, const lslam_grid_params *g,
+                      const lslam_fieldscore_params *p);
 
 #ifdef __cplusplus
 }

@@ -40,6 +40,9 @@ RAYCAST_BAD_POSE = 1
 RAYCAST_INVALID, RAYCAST_MATCH, RAYCAST_NOVEL, RAYCAST_THROUGH, RAYCAST_UNMAPPED = 0, 1, 2, 3, 4  # cls & 15
 RAYCAST_KIND_NONE, RAYCAST_KIND_UNKNOWN, RAYCAST_KIND_OCC = 0, 1, 2  # cls >> 4
 RECENTRE_BAD_POSE, RECENTRE_MOVED, RECENTRE_CLEARED = 1, 2, 4
+DIST_OCC, DIST_NOT_FREE = 0, 1  # lslam_dist_params.mode
+DIST_EMPTY = 1
+FIELD_BAD_POSE = 1
 
 
 class HIPLibraryError(RuntimeError):
@@ -162,6 +165,24 @@ class RecentreBatch(C.Structure):
                [(n, _VP) for n in ("pose", "origin", "logodds", "shift", "flags")]
 
 
+class DistParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("mode", "occ_min", "free_max", "d_max")]
+
+
+class DistBatch(C.Structure):
+    _fields_ = [("n_robots", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, _VP) for n in ("logodds", "d2", "n_src", "flags")]
+
+
+class FieldScoreParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("trunc2", "near2", "off2", "reserved")]
+
+
+class FieldScoreBatch(C.Structure):
+    _fields_ = [("n_robots", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, _VP) for n in ("xy", "pt_off", "pose", "origin", "d2", "rot", "stats", "clear2", "flags")]
+
+
 assert C.sizeof(ChunkModel) == 112
 assert C.sizeof(LandmarkRec) == 56
 
@@ -181,6 +202,8 @@ EXPORTS = [
     "lslam_reloc_abi_sizes", "lslam_reloc_params_default", "lslam_map_relocalize", "lslam_set_reloc_budget",
     "lslam_raycast_abi_sizes", "lslam_raycast_params_default", "lslam_grid_raycast",
     "lslam_recentre_abi_sizes", "lslam_recentre_params_default", "lslam_grid_recentre",
+    "lslam_dist_abi_sizes", "lslam_dist_params_default", "lslam_fieldscore_params_default",
+    "lslam_grid_distance", "lslam_field_score",
 ]
 
 _lib = None
@@ -265,6 +288,11 @@ def load():
         "lslam_recentre_abi_sizes": ([P(i64), C.c_int], C.c_int),
         "lslam_recentre_params_default": ([P(RecentreParams)], C.c_int),
         "lslam_grid_recentre": ([_VP, P(RecentreBatch), P(GridParams), P(RecentreParams)], C.c_int),
+        "lslam_dist_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_dist_params_default": ([P(DistParams)], C.c_int),
+        "lslam_fieldscore_params_default": ([P(FieldScoreParams)], C.c_int),
+        "lslam_grid_distance": ([_VP, P(DistBatch), P(GridParams), P(DistParams)], C.c_int),
+        "lslam_field_score": ([_VP, P(FieldScoreBatch), P(GridParams), P(FieldScoreParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -307,10 +335,13 @@ def _check_abi(L):
     L.lslam_raycast_abi_sizes(got6, 2)
     got7 = (C.c_int64 * 2)()
     L.lslam_recentre_abi_sizes(got7, 2)
-    got = list(got) + list(got2) + list(got3) + list(got4) + list(got5) + list(got6) + list(got7)
+    got8 = (C.c_int64 * 4)()
+    L.lslam_dist_abi_sizes(got8, 4)
+    got = list(got) + list(got2) + list(got3) + list(got4) + list(got5) + list(got6) + list(got7) + list(got8)
     want = want + [C.sizeof(GridParams), C.sizeof(GridBatch), C.sizeof(MapMatchParams), C.sizeof(MapMatchBatch),
                    C.sizeof(MapFuseParams), C.sizeof(MapFuseBatch), C.sizeof(RelocParams), C.sizeof(RelocBatch),
-                   C.sizeof(RaycastParams), C.sizeof(RaycastBatch), C.sizeof(RecentreParams), C.sizeof(RecentreBatch)]
+                   C.sizeof(RaycastParams), C.sizeof(RaycastBatch), C.sizeof(RecentreParams), C.sizeof(RecentreBatch),
+                   C.sizeof(DistParams), C.sizeof(DistBatch), C.sizeof(FieldScoreParams), C.sizeof(FieldScoreBatch)]
     if list(got) != want:
         _err = HIPLibraryError("struct sizes differ between %s %s and the ctypes layouts %s"
                                % (LIB_PATH, list(got), want))
@@ -415,6 +446,22 @@ def raycast_params(**kw):
 def recentre_params(**kw):
     p = RecentreParams()
     load().lslam_recentre_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def dist_params(**kw):
+    p = DistParams()
+    load().lslam_dist_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def fieldscore_params(**kw):
+    p = FieldScoreParams()
+    load().lslam_fieldscore_params_default(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

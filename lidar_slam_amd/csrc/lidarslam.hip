@@ -11,7 +11,8 @@
 //   (the scan-to-map matcher's two kernels), lslam_mapfuse.h (the match-fusion kernel),
 //   lslam_reloc.h (the relocalisation kernels), lslam_raycast.h (the grid ray-cast kernel; one
 //   beam's walk is lslam_raycast_walk.h, plain C++), lslam_recentre.h (the grid recentre kernel; its
-//   shift rule and in-place plan are lslam_recentre_plan.h, plain C++);
+//   shift rule and in-place plan are lslam_recentre_plan.h, plain C++), lslam_dist.h (the distance
+//   field of the grid and its reader; the two 1-D passes are lslam_dist_core.h, plain C++);
 // the host side is included at the foot:
 //   lslam_hazards.h  which waits a call's producer needs (plain C++, no HIP)
 //   lslam_ctx.h      lslam_ctx, its grow-only device buffers and timers, create / destroy,
@@ -3063,6 +3064,8 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
 #include "lslam_raycast.h"
 // the grid recentre kernel: the one writer of origin, and the second of logodds
 #include "lslam_recentre.h"
+// the distance-field kernel and the field's reader, last: the existing kernels keep their place
+#include "lslam_dist.h"
 
 // ------------------------------------------------------------------------
 // host side: the context, then the launchers and entry points

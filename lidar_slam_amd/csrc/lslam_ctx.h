@@ -409,6 +409,13 @@ int lslam_recentre_abi_sizes(int64_t *sizes, int n) {
     return 2;
 }
 
+int lslam_dist_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[4] = {(int64_t)sizeof(lslam_dist_params), (int64_t)sizeof(lslam_dist_batch),
+                          (int64_t)sizeof(lslam_fieldscore_params), (int64_t)sizeof(lslam_fieldscore_batch)};
+    for (int i = 0; i < n && i < 4 && sizes; i++) sizes[i] = s[i];
+    return 4;
+}
+
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
     if (!c || (!dst && n)) return LSLAM_ERR_ARG;
     if (!n) return LSLAM_OK;
@@ -592,6 +599,25 @@ int lslam_recentre_params_default(lslam_recentre_params *p) {
     memset(p, 0, sizeof(*p));
     p->margin = 128;  // cells: a quarter of the default map; the grid moves before max_range reaches far past the edge
     p->quantum = 8;   // cells: 16 bytes of a row, the group every reader of the grid loads
+    return LSLAM_OK;
+}
+
+int lslam_dist_params_default(lslam_dist_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->mode = LSLAM_DIST_OCC;
+    p->occ_min = 85;    // the matchers' threshold: one hit's worth
+    p->free_max = -1;   // the ray caster's: p < 0.5
+    p->d_max = 64;      // cells: 1.28 m at the default cell, beyond any clearance a stop acts on
+    return LSLAM_OK;
+}
+
+int lslam_fieldscore_params_default(lslam_fieldscore_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->trunc2 = 625;    // 25 cells: an outlier costs no more
+    p->near2 = 4;       // two cells: the map's walls are one to two cells thick
+    p->off2 = 4096;     // the default d_max squared
     return LSLAM_OK;
 }
 

@@ -1277,6 +1277,102 @@ static int launch_recentre(lslam_ctx *c, const lslam_recentre_batch *b, const ls
     return LSLAM_OK;
 }
 
+// ---- distance field and its read (lslam_dist.h) ----
+
+static int dist_check_params(const lslam_dist_params *p) {
+    if (!p) return set_err(LSLAM_ERR_ARG, "dist: params is NULL");
+    if (p->mode != LSLAM_DIST_OCC && p->mode != LSLAM_DIST_NOT_FREE)
+        return set_err(LSLAM_ERR_ARG, "dist: mode must be LSLAM_DIST_OCC or LSLAM_DIST_NOT_FREE");
+    if (p->occ_min < -32768 || p->occ_min > 32767) return set_err(LSLAM_ERR_ARG, "dist: occ_min must be in [-32768, 32767]");
+    if (p->free_max < -32768 || p->free_max > 32767)
+        return set_err(LSLAM_ERR_ARG, "dist: free_max must be in [-32768, 32767]");
+    if (p->d_max < 1 || p->d_max > DIST_D_MAX) return set_err(LSLAM_ERR_ARG, "dist: d_max must be in [1, 255]");
+    return LSLAM_OK;
+}
+
+// The band of rows of a workgroup: all of a robot's rows when the robots alone fill the chip, else so
+// many bands that there are two workgroups to a CU (at most DIST_MAX_SLICES per robot), in whole
+// groups of DIST_NW rows; then shrunk until the workgroup's LDS leaves room for two on a CU, or at
+// least fits one.  0: not even a band of DIST_NW rows fits.
+static int dist_band_rows(int W, int hal, int64_t n_robots, int n_cus) {
+    const int64_t want = std::min<int64_t>(std::max<int64_t>((2 * (int64_t)n_cus + n_robots - 1) / n_robots, 1), DIST_MAX_SLICES);
+    int band = (int)((W + want - 1) / want);
+    band = (band + DIST_NW - 1) / DIST_NW * DIST_NW;
+    while (band > DIST_NW && dist_lds_bytes(W, dist_blocks(W, band, hal)) > DIST_LDS_TWO) band -= DIST_NW;
+    if (dist_lds_bytes(W, dist_blocks(W, band, hal)) <= DIST_LDS_TWO) return band;
+    // (no band leaves room for two: the largest that fits one)
+    band = (int)((W + want - 1) / want);
+    band = (band + DIST_NW - 1) / DIST_NW * DIST_NW;
+    while (band > DIST_NW && dist_lds_bytes(W, dist_blocks(W, band, hal)) > DIST_LDS_MAX) band -= DIST_NW;
+    return dist_lds_bytes(W, dist_blocks(W, band, hal)) <= DIST_LDS_MAX ? band : 0;
+}
+
+static int launch_dist(lslam_ctx *c, const lslam_dist_batch *b, const lslam_grid_params *g, const lslam_dist_params *p) {
+    static std::once_flag once;
+    std::call_once(once, [] {
+        set_max_lds(dist_kernel<8>);
+        set_max_lds(dist_kernel<1>);
+    });
+    DistArgs k;
+    memset(&k, 0, sizeof(k));
+    k.b = *b;
+    k.grid_w = g->grid_w;
+    k.d_max = p->d_max;
+    k.not_free = p->mode == LSLAM_DIST_NOT_FREE ? 1 : 0;
+    k.thr = k.not_free ? p->free_max + 1 : p->occ_min;
+    k.hal = std::min(p->d_max, g->grid_w) - 1;
+    k.band = dist_band_rows(k.grid_w, k.hal, b->n_robots, c->n_cus);
+    if (!k.band) return set_err(LSLAM_ERR_UNSUPPORTED, "dist: the bitmap of 2 d_max rows of this grid_w does not fit LDS");
+    k.n_slices = (k.grid_w + k.band - 1) / k.band;
+    k.nblk = dist_blocks(k.grid_w, k.band, k.hal);
+    const int lds = dist_lds_bytes(k.grid_w, k.nblk);
+    const int64_t n = b->n_robots;
+    if (n * k.n_slices >= ((int64_t)1 << 31)) return set_err(LSLAM_ERR_UNSUPPORTED, "dist: too many robots in one call");
+    const bool vec = g->grid_w % 8 == 0 && (((uintptr_t)b->logodds | (uintptr_t)b->d2) & 15) == 0;
+    HIPCHK(hipMemsetAsync(b->n_src, 0, (size_t)n * 4, c->stream));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)b->flags, LSLAM_DIST_EMPTY, (size_t)n, c->stream));
+    if (vec) hipLaunchKernelGGL(dist_kernel<8>, dim3((unsigned)(n * k.n_slices)), dim3(DIST_TPB), lds, c->stream, k);
+    else hipLaunchKernelGGL(dist_kernel<1>, dim3((unsigned)(n * k.n_slices)), dim3(DIST_TPB), lds, c->stream, k);
+    HIPCHK(hipGetLastError());
+    c->hz.outs.add(b->d2, (size_t)n * (size_t)g->grid_w * (size_t)g->grid_w * 2);
+    c->hz.outs.add(b->n_src, (size_t)n * 4);
+    c->hz.outs.add(b->flags, (size_t)n * 4);
+    return LSLAM_OK;
+}
+
+static int fieldscore_check_params(const lslam_fieldscore_params *p) {
+    if (!p) return set_err(LSLAM_ERR_ARG, "fieldscore: params is NULL");
+    if (p->trunc2 < 1 || p->trunc2 > 65025) return set_err(LSLAM_ERR_ARG, "fieldscore: trunc2 must be in [1, 65025]");
+    if (p->near2 < 0 || p->near2 > 65025) return set_err(LSLAM_ERR_ARG, "fieldscore: near2 must be in [0, 65025]");
+    if (p->off2 < 0 || p->off2 > 65025) return set_err(LSLAM_ERR_ARG, "fieldscore: off2 must be in [0, 65025]");
+    return LSLAM_OK;
+}
+
+// One workgroup per (robot, slice of its points), by launch_raycast's rule.
+static int launch_fieldscore(lslam_ctx *c, const lslam_fieldscore_batch *b, const lslam_grid_params *g,
+                             const lslam_fieldscore_params *p) {
+    FieldScoreArgs k;
+    memset(&k, 0, sizeof(k));
+    k.b = *b;
+    k.inv = 1.0 / g->cell;
+    k.max_r2 = g->max_range * g->max_range;
+    k.grid_w = g->grid_w;
+    k.trunc2 = p->trunc2;
+    k.near2 = p->near2;
+    k.off2 = p->off2;
+    const int64_t n = b->n_robots, want = 2 * (int64_t)c->n_cus;
+    k.n_slices = (int)std::min<int64_t>(std::max<int64_t>((want + n - 1) / n, 1), FIELDSCORE_MAX_SLICES);
+    if (n * k.n_slices >= ((int64_t)1 << 31)) return set_err(LSLAM_ERR_UNSUPPORTED, "fieldscore: too many robots in one call");
+    HIPCHK(hipMemsetAsync(b->stats, 0, (size_t)n * 32, c->stream));
+    hipLaunchKernelGGL(fieldscore_kernel, dim3((unsigned)(n * k.n_slices)), dim3(FIELDSCORE_TPB), 0, c->stream, k);
+    HIPCHK(hipGetLastError());
+    c->hz.outs.add(b->rot, (size_t)n * 16);
+    c->hz.outs.add(b->stats, (size_t)n * 32);
+    c->hz.outs.add(b->clear2, (size_t)n * 4);
+    c->hz.outs.add(b->flags, (size_t)n * 4);
+    return LSLAM_OK;
+}
+
 // ---- express-scan codec (lslam_express.h) ----
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1580,6 +1676,46 @@ int lslam_grid_recentre(lslam_ctx *c, const lslam_recentre_batch *b, const lslam
     if (b->n_robots == 0) return LSLAM_OK;
     HIPCHK(hipSetDevice(c->device));
     return launch_recentre(c, b, g, p);
+}
+
+// On the main stream, as lslam_grid_raycast: after the calls that wrote the grid.
+int lslam_grid_distance(lslam_ctx *c, const lslam_dist_batch *b, const lslam_grid_params *g, const lslam_dist_params *p) {
+    int st = grid_check_params(g);
+    if (st) return st;
+    if ((st = dist_check_params(p))) return st;
+    if (!b) return set_err(LSLAM_ERR_ARG, "dist: batch is NULL");
+    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "dist: negative n_robots");
+    if (b->n_robots > 0) {
+        if (!b->logodds) return set_err(LSLAM_ERR_ARG, "dist: missing input (logodds)");
+        if (!b->d2 || !b->n_src || !b->flags) return set_err(LSLAM_ERR_ARG, "dist: missing output (d2, n_src, flags)");
+        const uintptr_t bytes = (uintptr_t)b->n_robots * (uintptr_t)g->grid_w * (uintptr_t)g->grid_w * 2;
+        const uintptr_t l0 = (uintptr_t)b->logodds, d0 = (uintptr_t)b->d2;
+        if (l0 < d0 + bytes && d0 < l0 + bytes) return set_err(LSLAM_ERR_ARG, "dist: d2 overlaps logodds");
+    }
+    if (!c) return set_err(LSLAM_ERR_ARG, "dist: ctx is NULL");
+    if (b->n_robots == 0) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return launch_dist(c, b, g, p);
+}
+
+// On the main stream, as lslam_grid_raycast.
+int lslam_field_score(lslam_ctx *c, const lslam_fieldscore_batch *b, const lslam_grid_params *g,
+                      const lslam_fieldscore_params *p) {
+    int st = grid_check_params(g);
+    if (st) return st;
+    if ((st = fieldscore_check_params(p))) return st;
+    if (!b) return set_err(LSLAM_ERR_ARG, "fieldscore: batch is NULL");
+    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "fieldscore: negative n_robots");
+    if (b->n_robots > 0) {
+        if (!b->xy || !b->pt_off || !b->pose || !b->origin || !b->d2)
+            return set_err(LSLAM_ERR_ARG, "fieldscore: missing input (xy, pt_off, pose, origin, d2)");
+        if (!b->rot || !b->stats || !b->clear2 || !b->flags)
+            return set_err(LSLAM_ERR_ARG, "fieldscore: missing output (rot, stats, clear2, flags)");
+    }
+    if (!c) return set_err(LSLAM_ERR_ARG, "fieldscore: ctx is NULL");
+    if (b->n_robots == 0) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return launch_fieldscore(c, b, g, p);
 }
 
 // (the scratch is sized per call: a call in flight keeps the chunking it was launched with)

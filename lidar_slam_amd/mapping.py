@@ -29,6 +29,7 @@ from .slam import LandmarkMap, MapInput
 
 GRID_BAD_POSE, GRID_CLIPPED = _lib.GRID_BAD_POSE, _lib.GRID_CLIPPED
 RECENTRE_BAD_POSE, RECENTRE_MOVED, RECENTRE_CLEARED = _lib.RECENTRE_BAD_POSE, _lib.RECENTRE_MOVED, _lib.RECENTRE_CLEARED
+DIST_OCC, DIST_NOT_FREE, DIST_EMPTY, FIELD_BAD_POSE = _lib.DIST_OCC, _lib.DIST_NOT_FREE, _lib.DIST_EMPTY, _lib.FIELD_BAD_POSE
 TILE = 64  # cells a side of the kernel's tile (lslam_grid.h GRID_T): the tests place rays on its seams
 
 
@@ -305,3 +306,115 @@ class GridRayCaster:
         c = self.counts.download().astype(np.int64)
         den = c[:, 1:5].sum(1) - c[:, 5]
         return np.where(den > 0, (c[:, _lib.RAYCAST_NOVEL] + c[:, _lib.RAYCAST_THROUGH]) / np.maximum(den, 1), 0.0)
+
+
+class DistanceField:
+    """The exact distance field of ``grid`` (``lslam_grid_distance``): per cell the squared Euclidean
+    distance, in cells, to the nearest source cell, saturated at ``d_max``^2; and its read under a
+    revolution (``lslam_field_score``): how far the returns lie from the map's sources, and the robot's
+    own clearance.  ``params``: mode (``DIST_OCC``: sources are the cells with L >= occ_min;
+    ``DIST_NOT_FREE``: the cells with L > free_max and everything off the map), occ_min, free_max,
+    d_max (``lslam_dist_params``; defaults OCC, 85, -1, 64 cells) and trunc2, near2
+    (``lslam_fieldscore_params``; defaults 625, 4); off2 is d_max^2.  The grid's geometry and its
+    device buffers are ``grid``'s, read in place::
+
+        grid.step(xy, scan_chunk_off, chunk_pt_off, pose=lm)
+        field.step()                                          # the field of the grid as it now stands
+        field.score(xy, scan_chunk_off, chunk_pt_off, pose=lm)
+        if field.clearance_mm().min() < 300.0: ...            # a robot is close to something
+
+    The field is recomputed whole by every ``step``: there is no incremental update after a
+    revolution.  After an ``OccupancyGrid.recentre`` the next ``step`` computes the moved grid's field
+    and ``score`` reads the moved origin on the device.  The definitions are the comments on the two
+    entry points in include/lidarslam.h; tests/dist_ref.py and tests/fieldscore_ref.py are their NumPy
+    forms and the kernels match them bit for bit."""
+
+    def __init__(self, grid: OccupancyGrid, **params):
+        self.grid, self.ctx, self.R = grid, grid.ctx, grid.R
+        ctx, R, W = self.ctx, self.R, grid.W
+        dk = {k: int(params.pop(k)) for k in ("mode", "occ_min", "free_max", "d_max") if k in params}
+        sk = {k: int(params.pop(k)) for k in ("trunc2", "near2") if k in params}
+        if params:
+            raise TypeError("unknown parameters: %s" % ", ".join(sorted(params)))
+        self.p = _lib.dist_params(**dk)
+        self.q = _lib.fieldscore_params(off2=min(int(self.p.d_max) ** 2, 65025), **sk)
+        # (a range error of params surfaces here, before anything large is allocated)
+        L = _lib.load()
+        _lib.check(L.lslam_grid_distance(ctx.handle, C.byref(_lib.DistBatch()), C.byref(grid.p), C.byref(self.p)),
+                   "lslam_grid_distance")
+        _lib.check(L.lslam_field_score(ctx.handle, C.byref(_lib.FieldScoreBatch()), C.byref(grid.p), C.byref(self.q)),
+                   "lslam_field_score")
+        self.d2 = ctx.empty((R, W, W), np.uint16)
+        self.n_src = ctx.empty(R, np.int32)
+        self.flags = ctx.empty(R, np.int32)
+        self.rot = ctx.empty((R, 2), np.float64)
+        self.stats = ctx.empty((R, 4), np.int64)
+        self.clear2 = ctx.empty(R, np.int32)
+        self.score_flags = ctx.empty(R, np.int32)
+        for a in (self.n_src, self.flags, self.rot, self.stats, self.clear2, self.score_flags):
+            a.fill_zero()
+        self._xy = _Grow(ctx, np.float64)
+        self._off = ctx.empty(R + 1, np.int32)
+        self._pose = ctx.empty((R, 3), np.float64)
+        self._off_host = np.zeros(R + 1, np.int64)
+        self.steps = self.scores = 0
+
+    def step(self, sync=True):
+        """The field of the grid's device buffer as it now stands."""
+        ctx, g = self.ctx, self.grid
+        b = _lib.DistBatch()
+        b.n_robots = self.R
+        b.logodds, b.d2, b.n_src, b.flags = g.logodds.addr, self.d2.addr, self.n_src.addr, self.flags.addr
+        _lib.check(_lib.load().lslam_grid_distance(ctx.handle, C.byref(b), C.byref(g.p), C.byref(self.p)),
+                   "lslam_grid_distance")
+        self.steps += 1
+        if sync:
+            ctx.sync()
+
+    def score(self, xy, scan_chunk_off=None, chunk_pt_off=None, pose=None, sync=True):
+        """One revolution per robot read in the field of the last ``step``, in the argument forms of
+        ``OccupancyGrid.step``; ``pose`` [R, 3]: a host array, a float64 ``DeviceArray`` (``lm.x``) or a
+        ``LandmarkMap``."""
+        if not self.steps:
+            raise ValueError("no step yet: the field has not been computed")
+        ctx, g = self.ctx, self.grid
+        dxy, doff, dpose = _stage_revolution(self, xy, scan_chunk_off, chunk_pt_off, pose)
+        b = _lib.FieldScoreBatch()
+        b.n_robots = self.R
+        b.xy, b.pt_off, b.pose, b.origin, b.d2 = dxy.addr, doff.addr, dpose.addr, g.origin.addr, self.d2.addr
+        b.rot, b.stats, b.clear2, b.flags = self.rot.addr, self.stats.addr, self.clear2.addr, self.score_flags.addr
+        _lib.check(_lib.load().lslam_field_score(ctx.handle, C.byref(b), C.byref(g.p), C.byref(self.q)),
+                   "lslam_field_score")
+        self.scores += 1
+        if sync:
+            ctx.sync()
+
+    def results(self):
+        """The last step's d2 [R, W, W] uint16, n_src [R], flags [R] (``DIST_EMPTY``)."""
+        if not self.steps:
+            raise ValueError("no step yet")
+        return {"d2": self.d2.download(), "n_src": self.n_src.download(), "flags": self.flags.download()}
+
+    def score_results(self):
+        """The last score's stats [R, 4] int64 (sum of min(v, trunc2), points scored, near points,
+        points off the map), clear2 [R], rot [R, 2], flags [R] (``FIELD_BAD_POSE``)."""
+        if not self.scores:
+            raise ValueError("no score yet")
+        return {"stats": self.stats.download(), "clear2": self.clear2.download(), "rot": self.rot.download(),
+                "flags": self.score_flags.download()}
+
+    def clearance_mm(self):
+        """Per robot, cell * sqrt(clear2): the distance from the robot cell of the last ``score`` to the
+        nearest source, saturated at cell * d_max (0 for a bad pose)."""
+        return float(self.grid.p.cell) * np.sqrt(self.clear2.download().astype(np.float64))
+
+    def near_share(self):
+        """Per robot, near points / points scored (0 where there are none)."""
+        s = self.stats.download()
+        return np.where(s[:, 1] > 0, s[:, 2] / np.maximum(s[:, 1], 1), 0.0)
+
+    def mean_d2(self):
+        """Per robot, the mean of min(v, trunc2) over the points scored (0 where there are none): the
+        beam-end-point score, in squared cells."""
+        s = self.stats.download()
+        return np.where(s[:, 1] > 0, s[:, 0] / np.maximum(s[:, 1], 1), 0.0)
