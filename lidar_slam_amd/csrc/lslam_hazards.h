@@ -53,8 +53,6 @@ struct RangeSet {
 };
 
 // What the producer (seed_kernel, rng_kernel) reads of a batch.
-// (Known gap: cut_lane_kernel on the seeding stream also reads the point arrays, which are not
-// tracked here.)
 struct ProducerInputs {
     const void *p[4];
     size_t n[4];
@@ -64,6 +62,23 @@ static inline ProducerInputs producer_inputs(const lslam_scan_batch *b) {
     return {{b->seeds, b->scan_chunk_off, b->chunk_pt_off, b->mt_state_in},
             {(size_t)b->n_scans * 4, (size_t)(b->n_scans + 1) * 4, (size_t)(b->n_chunks + 1) * 4,
              (size_t)b->n_scans * 625 * 4}};
+}
+
+// What cut_lane_kernel reads of a batch besides the CSR arrays: the points, xy or (xy == NULL) the
+// polar pair.  It runs on the seeding stream, which makes the producer's waits and no others.
+struct PointInputs {
+    const void *p[2];
+    size_t n[2];
+};
+static inline PointInputs point_inputs(const lslam_scan_batch *b) {
+    const size_t P = (size_t)b->n_points;
+    if (b->xy) return {{b->xy, nullptr}, {P * 16, 0}};
+    return {{b->theta_deg, b->dist_mm}, {P * 8, P * 8}};
+}
+// does the call launch cut_lane_kernel (launch_cuts)?  A fresh-stream call (only those seed, and
+// the cut kernel goes with seed_kernel) whose chunks fit chunk_kernel.
+static inline bool precomputes_cuts(const lslam_scan_batch *b) {
+    return !b->mt_state_in && b->n_chunks > 0 && b->max_chunk_points <= 128;
 }
 
 struct HazardState {
@@ -101,6 +116,11 @@ struct ProducerPlan {
     // 1.39 ms per step); otherwise the next call's producer runs beside it and holds the LDS
     // (C3 0.93 vs 1.03 ms)
     bool resolve_beside;
+    // A copy or an earlier call wrote the points and no wait of this plan covers it: launch no
+    // cut kernel, the stream-ordered consensus computes its cuts itself (byte-identical,
+    // test_gpu_cuts.py).  Asks for no wait and clears no set, so the producer still overlaps an
+    // upload of the points; false in a call that launches no cut kernel anyway.
+    bool skip_cuts;
 };
 
 // The waits of this call's producer; a wait that the plan asks for empties the set it covers.
@@ -128,5 +148,13 @@ static inline ProducerPlan plan_producer(HazardState &h, const lslam_scan_batch 
     if (!pl.spec) h.spec_run = 0;
     pl.wait_prev_slot = pl.hazard == 1 && !pl.spec;
     pl.resolve_beside = pl.hazard == 0 || pl.spec;
+    // after the clears above: a set that this plan's waits emptied no longer hits, and the seeding
+    // stream makes those waits ahead of the cut kernel (seed_beside)
+    pl.skip_cuts = false;
+    if (precomputes_cuts(b)) {
+        const PointInputs pt = point_inputs(b);
+        for (int i = 0; i < 2; i++)
+            if (pt.p[i] && pt.n[i]) pl.skip_cuts |= h.copies.hits(pt.p[i], pt.n[i]) || h.outs.hits(pt.p[i], pt.n[i]);
+    }
     return pl;
 }

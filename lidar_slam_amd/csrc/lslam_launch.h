@@ -359,11 +359,12 @@ static int launch_seed(lslam_ctx *c, KArgs &k, hipStream_t ss, int i) {
 }
 
 // chunk_kernel's chunks (at most 128 points): cut_lane_kernel on `ss` fills the next buffer of the
-// cut ring and k.cuts points the consensus at it.
-// (Known gap: the point arrays it reads are not among the inputs that `ss` waits for, producer_inputs.)
-static int launch_cuts(lslam_ctx *c, KArgs &k, hipStream_t ss) {
+// cut ring and k.cuts points the consensus at it.  `ss` makes the producer's waits only, so a call
+// whose points a pending copy or an earlier call wrote (pl.skip_cuts) launches none: the
+// consensus, ordered after both on the ctx stream, computes the cuts itself.
+static int launch_cuts(lslam_ctx *c, KArgs &k, const ProducerPlan &pl, hipStream_t ss) {
     k.cuts = nullptr;
-    if (k.b.n_chunks <= 0 || k.b.max_chunk_points > 128) return LSLAM_OK;
+    if (!precomputes_cuts(&k.b) || pl.skip_cuts) return LSLAM_OK;
     DevBuf &cb = c->cutb[c->cut_next];
     int st = cb.ensure(c, (size_t)k.b.n_chunks * sizeof(ChunkCut), "chunk cutoffs");
     if (st) return st;
@@ -392,7 +393,7 @@ static int seed_beside(lslam_ctx *c, KArgs &k, const ProducerPlan &pl, int &buf)
     if (pl.hazard == 2) HIPCHK(hipStreamWaitEvent(ss, c->ev_call, 0));
     int st = launch_seed(c, k, ss, i);
     if (st) return st;
-    if ((st = launch_cuts(c, k, ss))) return st;
+    if ((st = launch_cuts(c, k, pl, ss))) return st;
     HIPCHK(hipEventRecord(c->ev_seeded[i], ss));
     HIPCHK(hipStreamWaitEvent(c->pstream, c->ev_seeded[i], 0));
     c->seed_next ^= 1;

@@ -359,6 +359,76 @@ def test_fused_polar_loads_equal_polar_kernel_then_xy(ctx, hyp, n_beams, chunk):
     assert ra["landmarks"].tobytes() == rb["landmarks"].tobytes()
 
 
+@pytest.mark.parametrize("name", ["c3", "large"])
+def test_fused_polar_loads_vs_oracle(ctx, name):
+    """A1 fused into every point load against the CPU oracle on the reference's own xy
+    (synth.polar_to_xy_ref, NumPy's cos / sin; the kernels use OCML's): the C3-shaped batch on
+    fresh streams (cut_lane_kernel and chunk_kernel with polar loads) and 600-point chunks (model /
+    count / select kernels).  The coordinates may differ by DELTA0 at most; tests/test_polar_ref.py
+    proves from the oracle alone that no residual and no tie of these batches is within 16 times
+    that of changing a discrete output, so draws, per-trial counts, masks, winners (up to the same
+    pair drawn in the other order), flags and landmark decisions are exact and the real-valued
+    outputs within the xy path's tolerances against the golden (1e-9 relative, directions 1e-11)."""
+    import polar_ref as pr
+    from lidar_slam_amd import pipeline as pl
+    b, o = pr.batch(name), pr.batch_trials(name)
+    sco, cpo, T = b["scan_chunk_off"], b["chunk_pt_off"], b["trials"]
+    S, Cn = len(sco) - 1, int(sco[-1])
+    xy_dev = pl.polar_to_xy(ctx, b["theta_deg"], b["dist_mm"])
+    dxy = float(np.max(np.abs(xy_dev - b["xy"])))
+    p = pl.ScanPipeline(ctx, None, sco, cpo, theta_deg=b["theta_deg"], dist_mm=b["dist_mm"], seeds=b["seeds"],
+                        lmk_capacity=32, max_trials=T, want_counts=True, want_draws=True)
+    p.run()
+    r = p.results()
+    m = r["models"]
+    mask, yproj, models, lists = orc.run_batch(b["xy"], sco, cpo, b["seeds"], pr.THRESHOLD, T)
+    ref = {f: np.array([d[f] for d in models]) for f in m.dtype.names if f in models[0]}
+    n_mask = int(np.sum(r["mask"] != mask))
+    print("%s: max |xy - polar_to_xy_ref| = %.3g mm (DELTA0 %.3g); mask bytes differing: %d of %d"
+          % (name, dxy, pr.DELTA0, n_mask, mask.size))
+    assert dxy <= pr.DELTA0
+    assert np.array_equal(ref["n_draws"], [d["n_draws"] for d in o["models"]])  # run_batch chains as batch_trials does
+    assert np.array_equal(m["n_draws"], ref["n_draws"])
+    for c in range(Cn):  # the trials the oracle ran: draws 0 .. n_draws - 1, trials 0 .. n_draws - 2
+        nd = int(ref["n_draws"][c])
+        assert np.array_equal(r["draws"][c, :nd], o["draws"][c, :nd]), c
+        assert np.array_equal(r["counts"][c, :nd - 1], o["cnt"][c, :nd - 1]), c
+    assert n_mask == 0, "%d mask bytes differ" % n_mask
+    for f in ("n_inliers", "flags", "match_index", "landmark_id"):
+        assert np.array_equal(m[f], ref[f]), f
+    swapped = 0
+    for c in np.nonzero(m["best_trial"] != ref["best_trial"])[0]:
+        g, w = int(m["best_trial"][c]), int(ref["best_trial"][c])
+        assert g >= 0 and w >= 0, c
+        assert set(o["draws"][c, g].tolist()) == set(o["draws"][c, w].tolist()) and o["cnt"][c, g] == o["cnt"][c, w], c
+        swapped += 1
+    valid = (ref["flags"] & 1) != 0
+    assert int(valid.sum()) > Cn // 2
+    worst = {}
+    for f in ("ox", "oy", "a", "b", "tip_x", "tip_y", "proj_a", "proj_b"):
+        assert np.array_equal(np.isnan(m[f]), np.isnan(ref[f])), f
+        ok = ~np.isnan(ref[f])
+        worst[f] = float(np.max(_rel(m[f][ok], ref[f][ok]))) if ok.any() else 0.0
+    u = np.stack([m["ux"], m["uy"]], -1)[valid]
+    uref = np.stack([ref["ux"], ref["uy"]], -1)[valid]
+    worst["dir"] = float(np.max(np.minimum(np.max(np.abs(u - uref), -1), np.max(np.abs(u + uref), -1))))
+    worst["y_proj"] = float(np.max(_rel(r["y_proj"], yproj)))
+    assert np.array_equal(r["lmk_count"], [len(L) for L in lists])
+    worst["lmk"] = 0.0
+    for s in range(S):
+        got = r["landmarks"][s, :r["lmk_count"][s]]
+        assert list(got["id"]) == [L["id"] for L in lists[s]], s
+        assert list(got["life"]) == [L["life"] for L in lists[s]], s
+        for f, v in (("a", [L["a"] for L in lists[s]]), ("b", [L["b"] for L in lists[s]]),
+                     ("pos_x", [L["pos"][0] for L in lists[s]]), ("pos_y", [L["pos"][1] for L in lists[s]]),
+                     ("end_x", [L["end"][0] for L in lists[s]]), ("end_y", [L["end"][1] for L in lists[s]])):
+            if len(v):
+                worst["lmk"] = max(worst["lmk"], float(np.max(_rel(got[f], v))))
+    print("%s: winners with the pair swapped: %d; worst errors %s" % (name, swapped, worst))
+    assert worst.pop("dir") <= 1e-11
+    assert all(v < REL for v in worst.values()), worst
+
+
 def test_polar_to_xy(ctx):
     from lidar_slam_amd import pipeline as pl
     from lidar_slam_amd import synth

@@ -1,6 +1,7 @@
 """The producer's wait decisions (lidar_slam_amd/csrc/lslam_hazards.h), compiled with g++ on the CPU:
 the range sets of copies and call outputs, and plan_producer, which run_split turns into stream
-waits.  Addresses are integers cast to pointers; nothing is dereferenced.  The program is built
+waits -- and, for the points that the cut kernel reads on the seeding stream, into launching no
+cut kernel (points_copied, points_written).  Addresses are integers cast to pointers; nothing is dereferenced.  The program is built
 with -fsanitize=address,undefined when the compiler here can link an empty program with them."""
 import os
 import shutil
@@ -232,10 +233,143 @@ static void resync() {
     CHECK(waits == 2 && SPEC_RESYNC == 32 && h.spec_run == 6);
 }
 
+// The points that cut_lane_kernel reads on the seeding stream: xy [P][2] doubles, or theta_deg and
+// dist_mm [P] doubles each.  kind 0: xy (the polar pointers set too: xy wins); 1: polar.
+enum { P = 800 };
+static const uintptr_t PXY = 0x100000, PTH = 0x200000, PDD = 0x300000;
+static lslam_scan_batch pbatch(int kind, uintptr_t state_in = 0, uintptr_t state_out = 0) {
+    lslam_scan_batch b = batch(state_in, state_out);
+    b.n_points = P;
+    b.max_chunk_points = 128;
+    b.xy = kind == 0 ? (const double *)PXY : nullptr;
+    b.theta_deg = (const double *)PTH;
+    b.dist_mm = (const double *)PDD;
+    return b;
+}
+static const struct { int kind; uintptr_t at; size_t len; } PT[3] = {{0, PXY, P * 16}, {1, PTH, P * 8}, {1, PDD, P * 8}};
+
+// via: 0 a pending copy, 1 an earlier call's output
+static void note(HazardState &h, int via, uintptr_t at, size_t n) {
+    if (via) h.outs.add(A(at), n);
+    else h.copies.add(A(at), n);
+}
+static int noted(const HazardState &h, int via) { return via ? h.outs.n : h.copies.n; }
+// the cut kernel may not run ahead of the write: skipped, or behind a wait the seeding stream makes
+static bool cuts_safe(const ProducerPlan &pl, int via) { return pl.skip_cuts || (via ? pl.hazard == 2 : pl.wait_copy); }
+
+static void points_case(int via) {
+    for (int i = 0; i < 3; i++) {
+        const lslam_scan_batch b = pbatch(PT[i].kind);
+        const uintptr_t at = PT[i].at;
+        const size_t len = PT[i].len;
+        const uintptr_t lo[3] = {at, at - 8, at + len - 1};
+        const size_t n[3] = {len, 9, 100};
+        for (int v = 0; v < 3; v++) {
+            HazardState h;
+            note(h, via, FAR, 64);
+            note(h, via, lo[v], n[v]);
+            ProducerPlan pl = plan_producer(h, &b, 1);
+            CHECK(cuts_safe(pl, via));
+            // the points alone: the producer gains no wait, so nothing may be cleared
+            CHECK(pl.skip_cuts && !pl.wait_copy && pl.hazard == 0 && !pl.spec && !pl.wait_prev_slot && pl.resolve_beside);
+            CHECK(noted(h, via) == 2);
+            pl = plan_producer(h, &b, 1);  // still pending for the next call
+            CHECK(pl.skip_cuts && !pl.wait_copy && pl.hazard == 0);
+            // the seeds written as well: the seeding stream waits, the set is cleared, the cuts run
+            note(h, via, SEEDS, 4);
+            pl = plan_producer(h, &b, 1);
+            CHECK(cuts_safe(pl, via) && !pl.skip_cuts && noted(h, via) == 0);
+            CHECK(via ? (pl.hazard == 2 && !pl.wait_copy) : (pl.wait_copy && pl.hazard == 0));
+            CHECK(!plan_producer(h, &b, 1).skip_cuts);
+        }
+        // adjacent on either side: nothing asked
+        HazardState h;
+        note(h, via, at - 8, 8);
+        note(h, via, at + len, 8);
+        ProducerPlan pl = plan_producer(h, &b, 1);
+        CHECK(!pl.skip_cuts && !pl.wait_copy && pl.hazard == 0 && noted(h, via) == 2);
+        // a call that launches no cut kernel: a hit asks for nothing, the plan is the one without points
+        for (int why = 0; why < 3; why++) {
+            HazardState h1 = chained(), h2 = chained();
+            note(h1, via, at, len);
+            lslam_scan_batch nb = pbatch(PT[i].kind, why == 0 ? X : 0, Y);
+            if (why == 1) nb.max_chunk_points = 129;
+            if (why == 2) nb.n_chunks = 0;
+            lslam_scan_batch ref = nb;
+            ref.xy = nullptr;
+            ref.theta_deg = nullptr;
+            ref.dist_mm = nullptr;
+            const ProducerPlan a = plan_producer(h1, &nb, 1), r = plan_producer(h2, &ref, 1);
+            CHECK(!a.skip_cuts && !r.skip_cuts);
+            CHECK(a.wait_copy == r.wait_copy && a.hazard == r.hazard && a.spec == r.spec &&
+                  a.wait_prev_slot == r.wait_prev_slot && a.resolve_beside == r.resolve_beside);
+            CHECK(!a.wait_copy && a.hazard == (why == 0 ? 1 : 0) && a.spec == (why == 0));
+            CHECK(noted(h1, via) == 1 + via);  // (chained() holds one output)
+        }
+        // max_chunk_points = 128 is the last size with a cut kernel
+        {
+            HazardState h1;
+            note(h1, via, at, len);
+            lslam_scan_batch nb = pbatch(PT[i].kind);
+            nb.max_chunk_points = 1;
+            CHECK(plan_producer(h1, &nb, 1).skip_cuts);
+        }
+    }
+    // xy given: what lies where the polar arrays would be is not read, and the other way round
+    {
+        HazardState h;
+        note(h, via, PTH, P * 8);
+        note(h, via, PDD, P * 8);
+        const lslam_scan_batch b = pbatch(0);
+        CHECK(!plan_producer(h, &b, 1).skip_cuts);
+        const lslam_scan_batch pb = pbatch(1);
+        CHECK(plan_producer(h, &pb, 1).skip_cuts);
+    }
+    {
+        HazardState h;
+        note(h, via, PXY, P * 16);
+        const lslam_scan_batch pb = pbatch(1);
+        CHECK(!plan_producer(h, &pb, 1).skip_cuts);
+        const lslam_scan_batch b = pbatch(0);
+        CHECK(plan_producer(h, &b, 1).skip_cuts);
+    }
+    // absent points overlap nothing
+    {
+        HazardState h;
+        note(h, via, PXY, 0x300000);
+        lslam_scan_batch b = pbatch(1);
+        b.theta_deg = nullptr;
+        b.dist_mm = nullptr;
+        CHECK(!plan_producer(h, &b, 1).skip_cuts);
+        b = pbatch(0);
+        b.n_points = 0;
+        CHECK(!plan_producer(h, &b, 1).skip_cuts);
+    }
+    // a set that no longer knows what was written hits the points too
+    for (int kind = 0; kind < 2; kind++) {
+        HazardState h;
+        const int cap = via ? LSLAM_MAX_OUTS : LSLAM_MAX_COPIES;
+        for (int i = 0; i <= cap; i++) note(h, via, FAR + 256 * i, 64);
+        CHECK(via ? h.outs.overflow : h.copies.overflow);
+        lslam_scan_batch b = pbatch(kind);
+        const ProducerPlan pl = plan_producer(h, &b, 1);
+        CHECK(cuts_safe(pl, via));
+        // and in a call without a cut kernel it asks for what it asked before, no more
+        HazardState h2;
+        for (int i = 0; i <= cap; i++) note(h2, via, FAR + 256 * i, 64);
+        b.max_chunk_points = 129;
+        const ProducerPlan p2 = plan_producer(h2, &b, 1);
+        CHECK(!p2.skip_cuts && p2.wait_copy == !via && p2.hazard == (via ? 2 : 0));
+    }
+}
+static void points_copied() { points_case(0); }
+static void points_written() { points_case(1); }
+
 int main(int argc, char **argv) {
     const struct { const char *name; void (*fn)(); } cases[] = {
         {"copies", copies},       {"duplicates", duplicates},     {"overflow", overflow}, {"output_union", output_union},
-        {"chaining", chaining},   {"copy_between", copy_between}, {"resync", resync}};
+        {"chaining", chaining},   {"copy_between", copy_between}, {"resync", resync},     {"points_copied", points_copied},
+        {"points_written", points_written}};
     int ran = 0;
     for (const auto &c : cases)
         if (argc < 2 || !std::strcmp(argv[1], c.name)) {
@@ -247,7 +381,8 @@ int main(int argc, char **argv) {
 }
 """
 
-CASES = ["copies", "duplicates", "overflow", "output_union", "chaining", "copy_between", "resync"]
+CASES = ["copies", "duplicates", "overflow", "output_union", "chaining", "copy_between", "resync", "points_copied",
+         "points_written"]
 
 
 def _compiles(cmd, src, exe):
