@@ -563,6 +563,53 @@ typedef struct lslam_fieldscore_batch {
     int32_t *flags;           /* [n_robots] LSLAM_FIELD_* */
 } lslam_fieldscore_batch;
 
+/* ---- field-align flags (lslam_fieldalign_batch.flags) ---- */
+enum {
+    LSLAM_FIELDALIGN_BAD_POSE = 1,   /* as LSLAM_GRID_BAD_POSE: nothing is evaluated, pose_out is pose */
+    LSLAM_FIELDALIGN_CONVERGED = 2,  /* a step fell below eps_t and eps_r */
+    LSLAM_FIELDALIGN_SINGULAR = 4,   /* a pivot of the solve is not finite and > 0, or the stepped pose is not finite: pose_out is pose */
+    LSLAM_FIELDALIGN_FEW = 8,        /* an evaluation used fewer than min_points points: pose_out is pose */
+    LSLAM_FIELDALIGN_DIVERGED = 16,  /* the pose left the guess by more than max_shift or max_turn: pose_out is pose */
+    LSLAM_FIELDALIGN_WEAK = 32       /* the last evaluation used less than min_permille of the valid points: pose_out is pose */
+};
+
+/* Gauss-Newton alignment in the distance field (lslam_field_align), 72 bytes.  Lengths in cells unless
+ * said otherwise. */
+typedef struct lslam_fieldalign_params {
+    double trunc;      /* a point whose interpolated distance exceeds it is skipped; 0..255 (25.0, the square root
+                          of lslam_fieldscore_params.trunc2) */
+    double damp_t;     /* added to the two translation diagonals of J^T J; >= 0, finite (1.0) */
+    double damp_r;     /* added to its rotation diagonal; >= 0, finite (100.0) */
+    double eps_t;      /* cells: a step with max(|dx|, |dy|) below it ... */
+    double eps_r;      /* ... and |dtheta| below this many rad has converged; both >= 0, finite (0.01, 1e-4) */
+    double max_shift;  /* mm per axis: gate on the distance from the guess; >= 0, +inf: no gate (200.0) */
+    double max_turn;   /* rad: the same for the heading; >= 0, +inf: no gate (0.1) */
+    int32_t n_iter;        /* most steps, 1..32 (10) */
+    int32_t min_points;    /* an evaluation needs this many used points; >= 0 (16) */
+    int32_t min_permille;  /* gate on points used at the last evaluation / valid points, 0..1000 (500) */
+    int32_t reserved;
+} lslam_fieldalign_params;
+
+/* One revolution per robot aligned in the robot's field, 96 bytes; all pointers DEVICE memory, all
+ * required.  P = pt_off[n_robots], E = n_iter + 1. */
+typedef struct lslam_fieldalign_batch {
+    int32_t n_robots;
+    int32_t reserved;
+    /* inputs: as lslam_fieldscore_batch */
+    const double *xy;         /* [P][2] revolutions, each in its robot's frame */
+    const int32_t *pt_off;    /* [n_robots+1] CSR robot -> points */
+    const double *pose;       /* [n_robots][3] the guess (x mm, y mm, theta rad), e.g. the filter's ukf_x */
+    const double *origin;     /* [n_robots][2] world coordinates of the corner of cell (0, 0) */
+    const uint16_t *d2;       /* [n_robots][grid_w][grid_w] the field of lslam_grid_distance: read only */
+    /* outputs */
+    double *pose_out;         /* [n_robots][3] the aligned pose, or pose bit for bit; may be pose itself */
+    double *trace;            /* [n_robots][E][5] (px, py, theta, cos theta, sin theta) of every evaluation; zeros beyond the last */
+    int64_t *normal;          /* [n_robots][10] the last evaluation's sums: J^T J (xx, xy, xt, yy, yt, tt), J^T r (x, y, t), r^2; times 2^20 */
+    int32_t *n_used;          /* [n_robots][3] points used at the first evaluation, at the last, valid points within max_range */
+    int32_t *iters;           /* [n_robots] steps taken */
+    int32_t *flags;           /* [n_robots] LSLAM_FIELDALIGN_* */
+} lslam_fieldalign_batch;
+
 typedef struct lslam_ctx lslam_ctx;  /* opaque: device, stream, events, scratch */
 
 /* ---- library / context ---- */
@@ -612,6 +659,8 @@ int lslam_recentre_abi_sizes(int64_t *sizes, int n);
 /* and for lslam_dist_params, lslam_dist_batch, lslam_fieldscore_params, lslam_fieldscore_batch.
  * Writes min(n, 4) entries, returns 4. */
 int lslam_dist_abi_sizes(int64_t *sizes, int n);
+/* and for lslam_fieldalign_params, lslam_fieldalign_batch.  Writes min(n, 2) entries, returns 2. */
+int lslam_fieldalign_abi_sizes(int64_t *sizes, int n);
 /* per-kernel HIP-event timing on the ctx stream (kernel ids: LSLAM_K_*) */
 enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMARK = 3, LSLAM_K_UKF = 4,
        LSLAM_K_RNG = 5 /* parity-stream producer */, LSLAM_K_CONSENSUS = 6 /* per-chunk A4-A8 */,
@@ -651,6 +700,7 @@ int lslam_raycast_params_default(lslam_raycast_params *p);
 int lslam_recentre_params_default(lslam_recentre_params *p);
 int lslam_dist_params_default(lslam_dist_params *p);
 int lslam_fieldscore_params_default(lslam_fieldscore_params *p);
+int lslam_fieldalign_params_default(lslam_fieldalign_params *p);
 /* smallest e with RN(sqrt(e)) >= thr: (residual < thr) <=> (squared residual < cutoff) */
 double lslam_inlier_cutoff(double thr);
 /* MerweScaledSigmaPoints weights (filterpy _compute_weights) for n = 3 */
@@ -1011,6 +1061,84 @@ int lslam_grid_distance(lslam_ctx *ctx, const lslam_dist_batch *b, const lslam_g
  * checked before the context is touched; n_robots == 0 does nothing. */
 int lslam_field_score(lslam_ctx *ctx, const lslam_fieldscore_batch *b, const lslam_grid_params *g,
                       const lslam_fieldscore_params *p);
+
+/* Gauss-Newton pose refinement in the distance field: one revolution per robot, a pose guess and the
+ * robot's field -> the pose nearby at which the revolution's returns lie closest to the map's sources,
+ * by at most n_iter damped Gauss-Newton steps on the bilinearly interpolated field, and the normal
+ * equations of the alignment there.  A tracker's step (a few descents from the filter's pose); the
+ * correlative matchers and the relocaliser serve a robot that has lost track.  The grid's geometry is
+ * g's cell, grid_w and max_range (g is checked as lslam_grid_update checks it), W = grid_w,
+ * inv = 1.0 / cell, S = 20.  Per robot r, in FP64 with every operation rounded on its own (nothing is
+ * fused), then integers:
+ *   0. pose.  (px, py, theta) = pose[r], the guess.  A bad pose is step 0 of lslam_grid_update, verbatim
+ *      (a non-finite pose component or origin, or |X0d| or |Y0d| >= 2^20): flags[r] =
+ *      LSLAM_FIELDALIGN_BAD_POSE, pose_out[r] = pose[r] bit for bit, and trace, normal, n_used and iters
+ *      of the robot are zeros.
+ *   1. evaluation k = 0, 1, .. at the pose (px, py, theta) as it then stands.  (c, s) = the library's
+ *      cos and sin of theta; trace[r][k] = (px, py, theta, c, s), and the written bits of (c, s) are the
+ *      definition's input.  The points are those of lslam_grid_update steps 0-1: valid (both
+ *      coordinates finite, not exactly (0, 0)) and not beyond (x x + y y > max_range max_range); their
+ *      count, the same at every evaluation, is n_valid.  For each of them:
+ *        rx = c x - s y, ry = s x + c y, wx = px + rx, wy = py + ry;
+ *        u = (wx - ox) inv - 0.5, iu = floor(u), fu = u - iu; v = (wy - oy) inv - 0.5, iv = floor(v),
+ *        fv = v - iv: a field value belongs to the centre of its cell.  The point is skipped unless
+ *        0 <= iu <= W - 2 and 0 <= iv <= W - 2 (compared as doubles; a NaN fails): all four corners
+ *        (ix .. ix + 1, iy .. iy + 1), (ix, iy) = (iu, iv) as integers, lie on the map.
+ *        A corner's distance is dq(w) = (double)isqrt(65536 w) / 256.0 with the INTEGER square root
+ *        (floor), exact whatever a hardware square root rounds to: d00 = dq(d2[iy][ix]),
+ *        d10 = dq(d2[iy][ix + 1]), d01 = dq(d2[iy + 1][ix]), d11 = dq(d2[iy + 1][ix + 1]).
+ *        e0 = d10 - d00, e1 = d11 - d01, a0 = d00 + fu e0, a1 = d01 + fu e1, gy = a1 - a0,
+ *        m = a0 + fv gy, gx = e0 + fv (e1 - e0): the interpolated distance and its two partial
+ *        derivatives, in cells and cells per cell.  jt = (gy rx - gx ry) inv, its derivative by theta.
+ *        The point is skipped if m > trunc: an outlier costs nothing.  Otherwise it is used, and its
+ *        ten terms are, in this order, gx gx, gx gy, gx jt, gy gy, gy jt, jt jt, gx m, gy m, jt m, m m;
+ *        each term t is the int64 rint(t 2^S), round-half-even (the product by 2^S is exact).
+ *      N[0..9] = the sums of the ten terms over the used points, as integers: the order of lanes and
+ *      waves does not matter.  n_k = the number of used points.
+ *      Overflow: the field min(d, d_max) is 1-Lipschitz between neighbouring cells and dq floors it to
+ *      a multiple of 1/256, so |gx|, |gy| <= 1 + 1/256; max_range / cell <= 4096 bounds the lever arm,
+ *      |jt| <= (1 + 1/256) sqrt(2) 4096 < 5817; m <= trunc <= 255.  The largest term, jt jt 2^S, is
+ *      below 2^45.02, so the sums of up to 2^16 = 65536 points per robot stay below 2^61.1, inside
+ *      int64, and S = 20 stands.  A robot with more points than that is not supported.
+ *      If n_k < min_points: LSLAM_FIELDALIGN_FEW, and the iteration ends here.  If k = n_iter, or the
+ *      step before this evaluation set CONVERGED, the iteration ends here: this is the evaluation after
+ *      the last step.
+ *   2. step k (k < n_iter).  sc = 2^-S.  H00 = (double)N0 sc + damp_t, H01 = (double)N1 sc,
+ *      H02 = (double)N2 sc, H11 = (double)N3 sc + damp_t, H12 = (double)N4 sc, H22 = (double)N5 sc +
+ *      damp_r, g0 = (double)N6 sc, g1 = (double)N7 sc, g2 = (double)N8 sc (the conversions round to
+ *      nearest even).  LDL^T, a pivot being good iff it is > 0 and finite:
+ *        d0 = H00; l10 = H01 / d0, l20 = H02 / d0; d1 = H11 - l10 H01; t21 = H12 - l20 H01,
+ *        l21 = t21 / d1; d2 = (H22 - l20 H02) - l21 t21;
+ *        y0 = g0, y1 = g1 - l10 y0, y2 = (g2 - l20 y0) - l21 y1; z0 = y0 / d0, z1 = y1 / d1, z2 = y2 / d2;
+ *        x2 = z2, x1 = z1 - l21 x2, x0 = (z0 - l10 x1) - l20 x2; (dx, dy, dt) = (-x0, -x1, -x2),
+ *      dx and dy in cells, dt in rad: the solution of (J^T J + diag(damp_t, damp_t, damp_r)) delta =
+ *      -J^T r.  With positive damping the system is positive definite even in a corridor, and the
+ *      direction that the revolution does not observe does not move.  The stepped pose is
+ *      (px + dx cell, py + dy cell, theta + dt), no angle wrap.  If a pivot is bad (the pivots are
+ *      tested in order; the first bad one ends the solve) or a component of the stepped pose is not
+ *      finite: LSLAM_FIELDALIGN_SINGULAR, the pose stays, and the iteration ends here.  Otherwise the
+ *      pose becomes the stepped pose, iters[r] = k + 1, and LSLAM_FIELDALIGN_CONVERGED is set iff
+ *      max(|dx|, |dy|) < eps_t and |dt| < eps_r.  Evaluation k + 1 follows.
+ *   3. gates, on the pose (px, py, theta) as it stands at the end and the guess (px0, py0, theta0):
+ *      LSLAM_FIELDALIGN_DIVERGED iff |px - px0| > max_shift or |py - py0| > max_shift or
+ *      |theta - theta0| > max_turn; LSLAM_FIELDALIGN_WEAK iff 1000 n_last < min_permille n_valid (int64),
+ *      n_last the used points of the last evaluation made.
+ *   4. outputs.  pose_out[r] = the pose at the end, unless one of BAD_POSE, SINGULAR, FEW, DIVERGED,
+ *      WEAK is set: then pose[r] bit for bit (copied as 64-bit words).  normal[r] = N of the last
+ *      evaluation made; n_used[r] = (n_0, n_last, n_valid); iters[r]; flags[r]; rows of trace[r] beyond
+ *      the last evaluation made are zeros.  Everything but pose_out is reported as computed whatever
+ *      the flags.
+ * An EMPTY field has no gradient: every step is exactly zero, and CONVERGED comes with the first (if
+ * d_max <= trunc; otherwise every point is skipped).  H = normal[0..5] 2^-S and g = normal[6..8] 2^-S
+ * are the Gauss-Newton information matrix and vector of the alignment at pose_out, in cells and rad.
+ * pose_out may be pose (the filter's ukf_x): the one thread that writes a robot's outputs belongs to
+ * the one wave that read its pose, and writes after it (lslam_map_match step 5's rule).  The whole
+ * iteration is one launch (lslam_fieldalign.h).  Runs on the context's main stream, after every
+ * earlier call: it sees the field of a preceding lslam_grid_distance and the origin of a preceding
+ * lslam_grid_recentre.  Out-of-range parameters and missing pointers return LSLAM_ERR_ARG (the message
+ * names the field), checked before the context is touched; n_robots == 0 does nothing. */
+int lslam_field_align(lslam_ctx *ctx, const lslam_fieldalign_batch *b, const lslam_grid_params *g,
+                      const lslam_fieldalign_params *p);
 
 #ifdef __cplusplus
 }

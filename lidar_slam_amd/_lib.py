@@ -43,6 +43,8 @@ RECENTRE_BAD_POSE, RECENTRE_MOVED, RECENTRE_CLEARED = 1, 2, 4
 DIST_OCC, DIST_NOT_FREE = 0, 1  # lslam_dist_params.mode
 DIST_EMPTY = 1
 FIELD_BAD_POSE = 1
+(FIELDALIGN_BAD_POSE, FIELDALIGN_CONVERGED, FIELDALIGN_SINGULAR, FIELDALIGN_FEW, FIELDALIGN_DIVERGED,
+ FIELDALIGN_WEAK) = 1, 2, 4, 8, 16, 32
 
 
 class HIPLibraryError(RuntimeError):
@@ -183,6 +185,17 @@ class FieldScoreBatch(C.Structure):
                [(n, _VP) for n in ("xy", "pt_off", "pose", "origin", "d2", "rot", "stats", "clear2", "flags")]
 
 
+class FieldAlignParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("trunc", "damp_t", "damp_r", "eps_t", "eps_r", "max_shift", "max_turn")] + \
+               [(n, C.c_int32) for n in ("n_iter", "min_points", "min_permille", "reserved")]
+
+
+class FieldAlignBatch(C.Structure):
+    _fields_ = [("n_robots", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, _VP) for n in ("xy", "pt_off", "pose", "origin", "d2", "pose_out", "trace", "normal", "n_used",
+                                   "iters", "flags")]
+
+
 assert C.sizeof(ChunkModel) == 112
 assert C.sizeof(LandmarkRec) == 56
 
@@ -204,6 +217,7 @@ EXPORTS = [
     "lslam_recentre_abi_sizes", "lslam_recentre_params_default", "lslam_grid_recentre",
     "lslam_dist_abi_sizes", "lslam_dist_params_default", "lslam_fieldscore_params_default",
     "lslam_grid_distance", "lslam_field_score",
+    "lslam_fieldalign_abi_sizes", "lslam_fieldalign_params_default", "lslam_field_align",
 ]
 
 _lib = None
@@ -293,6 +307,9 @@ def load():
         "lslam_fieldscore_params_default": ([P(FieldScoreParams)], C.c_int),
         "lslam_grid_distance": ([_VP, P(DistBatch), P(GridParams), P(DistParams)], C.c_int),
         "lslam_field_score": ([_VP, P(FieldScoreBatch), P(GridParams), P(FieldScoreParams)], C.c_int),
+        "lslam_fieldalign_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_fieldalign_params_default": ([P(FieldAlignParams)], C.c_int),
+        "lslam_field_align": ([_VP, P(FieldAlignBatch), P(GridParams), P(FieldAlignParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -337,11 +354,15 @@ def _check_abi(L):
     L.lslam_recentre_abi_sizes(got7, 2)
     got8 = (C.c_int64 * 4)()
     L.lslam_dist_abi_sizes(got8, 4)
-    got = list(got) + list(got2) + list(got3) + list(got4) + list(got5) + list(got6) + list(got7) + list(got8)
+    got9 = (C.c_int64 * 2)()
+    L.lslam_fieldalign_abi_sizes(got9, 2)
+    got = (list(got) + list(got2) + list(got3) + list(got4) + list(got5) + list(got6) + list(got7) + list(got8)
+           + list(got9))
     want = want + [C.sizeof(GridParams), C.sizeof(GridBatch), C.sizeof(MapMatchParams), C.sizeof(MapMatchBatch),
                    C.sizeof(MapFuseParams), C.sizeof(MapFuseBatch), C.sizeof(RelocParams), C.sizeof(RelocBatch),
                    C.sizeof(RaycastParams), C.sizeof(RaycastBatch), C.sizeof(RecentreParams), C.sizeof(RecentreBatch),
-                   C.sizeof(DistParams), C.sizeof(DistBatch), C.sizeof(FieldScoreParams), C.sizeof(FieldScoreBatch)]
+                   C.sizeof(DistParams), C.sizeof(DistBatch), C.sizeof(FieldScoreParams), C.sizeof(FieldScoreBatch),
+                   C.sizeof(FieldAlignParams), C.sizeof(FieldAlignBatch)]
     if list(got) != want:
         _err = HIPLibraryError("struct sizes differ between %s %s and the ctypes layouts %s"
                                % (LIB_PATH, list(got), want))
@@ -462,6 +483,14 @@ def dist_params(**kw):
 def fieldscore_params(**kw):
     p = FieldScoreParams()
     load().lslam_fieldscore_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def fieldalign_params(**kw):
+    p = FieldAlignParams()
+    load().lslam_fieldalign_params_default(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

@@ -416,6 +416,12 @@ int lslam_dist_abi_sizes(int64_t *sizes, int n) {
     return 4;
 }
 
+int lslam_fieldalign_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[2] = {(int64_t)sizeof(lslam_fieldalign_params), (int64_t)sizeof(lslam_fieldalign_batch)};
+    for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
+    return 2;
+}
+
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
     if (!c || (!dst && n)) return LSLAM_ERR_ARG;
     if (!n) return LSLAM_OK;
@@ -618,6 +624,22 @@ int lslam_fieldscore_params_default(lslam_fieldscore_params *p) {
     p->trunc2 = 625;    // 25 cells: an outlier costs no more
     p->near2 = 4;       // two cells: the map's walls are one to two cells thick
     p->off2 = 4096;     // the default d_max squared
+    return LSLAM_OK;
+}
+
+int lslam_fieldalign_params_default(lslam_fieldalign_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->trunc = 25.0;       // cells: the square root of the score's trunc2; an outlier costs nothing
+    p->damp_t = 1.0;       // one point's worth of gradient: a corridor's free direction stays put
+    p->damp_r = 100.0;     // one point's worth at a lever arm of ten cells
+    p->eps_t = 0.01;       // cells: 0.2 mm at the default cell, far below the range noise
+    p->eps_r = 1e-4;       // rad: 0.01 cell at a lever arm of 100 cells
+    p->max_shift = 200.0;  // mm: ten default cells, inside the basin that trunc leaves
+    p->max_turn = 0.1;     // rad: beyond it the guess was lost, which is the matchers' case
+    p->n_iter = 10;
+    p->min_points = 16;    // three unknowns, with room for the outliers among them
+    p->min_permille = 500;
     return LSLAM_OK;
 }
 

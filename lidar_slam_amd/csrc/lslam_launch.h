@@ -1374,6 +1374,52 @@ static int launch_fieldscore(lslam_ctx *c, const lslam_fieldscore_batch *b, cons
     return LSLAM_OK;
 }
 
+// ---- alignment in the field (lslam_fieldalign.h) ----
+
+static int fieldalign_check_params(const lslam_fieldalign_params *p) {
+    if (!p) return set_err(LSLAM_ERR_ARG, "fieldalign: params is NULL");
+    if (!(p->trunc >= 0.0 && p->trunc <= 255.0)) return set_err(LSLAM_ERR_ARG, "fieldalign: trunc must be in [0, 255]");
+    if (!(p->damp_t >= 0.0) || !std::isfinite(p->damp_t)) return set_err(LSLAM_ERR_ARG, "fieldalign: damp_t must be >= 0 and finite");
+    if (!(p->damp_r >= 0.0) || !std::isfinite(p->damp_r)) return set_err(LSLAM_ERR_ARG, "fieldalign: damp_r must be >= 0 and finite");
+    if (!(p->eps_t >= 0.0) || !std::isfinite(p->eps_t)) return set_err(LSLAM_ERR_ARG, "fieldalign: eps_t must be >= 0 and finite");
+    if (!(p->eps_r >= 0.0) || !std::isfinite(p->eps_r)) return set_err(LSLAM_ERR_ARG, "fieldalign: eps_r must be >= 0 and finite");
+    if (!(p->max_shift >= 0.0)) return set_err(LSLAM_ERR_ARG, "fieldalign: max_shift must be >= 0");
+    if (!(p->max_turn >= 0.0)) return set_err(LSLAM_ERR_ARG, "fieldalign: max_turn must be >= 0");
+    if (p->n_iter < 1 || p->n_iter > FIELDALIGN_MAX_ITER) return set_err(LSLAM_ERR_ARG, "fieldalign: n_iter must be in [1, 32]");
+    if (p->min_points < 0) return set_err(LSLAM_ERR_ARG, "fieldalign: min_points must be >= 0");
+    if (p->min_permille < 0 || p->min_permille > 1000) return set_err(LSLAM_ERR_ARG, "fieldalign: min_permille must be in [0, 1000]");
+    return LSLAM_OK;
+}
+
+// One wave per robot, FIELDALIGN_RPB robots to a workgroup.
+static int launch_fieldalign(lslam_ctx *c, const lslam_fieldalign_batch *b, const lslam_grid_params *g,
+                             const lslam_fieldalign_params *p) {
+    FieldAlignArgs k;
+    memset(&k, 0, sizeof(k));
+    k.b = *b;
+    k.p = *p;
+    k.cell = g->cell;
+    k.inv = 1.0 / g->cell;
+    k.max_r2 = g->max_range * g->max_range;
+    k.grid_w = g->grid_w;
+    const size_t n = (size_t)b->n_robots, rows = (size_t)p->n_iter + 1;
+    // (pose_out is written for every robot; the rest is zeros where the kernel writes nothing)
+    HIPCHK(hipMemsetAsync(b->trace, 0, n * rows * 40, c->stream));
+    HIPCHK(hipMemsetAsync(b->normal, 0, n * 80, c->stream));
+    HIPCHK(hipMemsetAsync(b->n_used, 0, n * 12, c->stream));
+    HIPCHK(hipMemsetAsync(b->iters, 0, n * 4, c->stream));
+    const unsigned blocks = (unsigned)((n + FIELDALIGN_RPB - 1) / FIELDALIGN_RPB);
+    hipLaunchKernelGGL(fieldalign_kernel, dim3(blocks), dim3(FIELDALIGN_TPB), 0, c->stream, k);
+    HIPCHK(hipGetLastError());
+    c->hz.outs.add(b->pose_out, n * 24);
+    c->hz.outs.add(b->trace, n * rows * 40);
+    c->hz.outs.add(b->normal, n * 80);
+    c->hz.outs.add(b->n_used, n * 12);
+    c->hz.outs.add(b->iters, n * 4);
+    c->hz.outs.add(b->flags, n * 4);
+    return LSLAM_OK;
+}
+
 // ---- express-scan codec (lslam_express.h) ----
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1717,6 +1763,26 @@ int lslam_field_score(lslam_ctx *c, const lslam_fieldscore_batch *b, const lslam
     if (b->n_robots == 0) return LSLAM_OK;
     HIPCHK(hipSetDevice(c->device));
     return launch_fieldscore(c, b, g, p);
+}
+
+// On the main stream, as lslam_field_score.
+int lslam_field_align(lslam_ctx *c, const lslam_fieldalign_batch *b, const lslam_grid_params *g,
+                      const lslam_fieldalign_params *p) {
+    int st = grid_check_params(g);
+    if (st) return st;
+    if ((st = fieldalign_check_params(p))) return st;
+    if (!b) return set_err(LSLAM_ERR_ARG, "fieldalign: batch is NULL");
+    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "fieldalign: negative n_robots");
+    if (b->n_robots > 0) {
+        if (!b->xy || !b->pt_off || !b->pose || !b->origin || !b->d2)
+            return set_err(LSLAM_ERR_ARG, "fieldalign: missing input (xy, pt_off, pose, origin, d2)");
+        if (!b->pose_out || !b->trace || !b->normal || !b->n_used || !b->iters || !b->flags)
+            return set_err(LSLAM_ERR_ARG, "fieldalign: missing output (pose_out, trace, normal, n_used, iters, flags)");
+    }
+    if (!c) return set_err(LSLAM_ERR_ARG, "fieldalign: ctx is NULL");
+    if (b->n_robots == 0) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return launch_fieldalign(c, b, g, p);
 }
 
 // (the scratch is sized per call: a call in flight keeps the chunking it was launched with)

@@ -30,6 +30,12 @@ from .slam import LandmarkMap, MapInput
 GRID_BAD_POSE, GRID_CLIPPED = _lib.GRID_BAD_POSE, _lib.GRID_CLIPPED
 RECENTRE_BAD_POSE, RECENTRE_MOVED, RECENTRE_CLEARED = _lib.RECENTRE_BAD_POSE, _lib.RECENTRE_MOVED, _lib.RECENTRE_CLEARED
 DIST_OCC, DIST_NOT_FREE, DIST_EMPTY, FIELD_BAD_POSE = _lib.DIST_OCC, _lib.DIST_NOT_FREE, _lib.DIST_EMPTY, _lib.FIELD_BAD_POSE
+FIELDALIGN_BAD_POSE, FIELDALIGN_CONVERGED, FIELDALIGN_SINGULAR = _lib.FIELDALIGN_BAD_POSE, _lib.FIELDALIGN_CONVERGED, _lib.FIELDALIGN_SINGULAR
+FIELDALIGN_FEW, FIELDALIGN_DIVERGED, FIELDALIGN_WEAK = _lib.FIELDALIGN_FEW, _lib.FIELDALIGN_DIVERGED, _lib.FIELDALIGN_WEAK
+# an alignment with one of these left pose_out as the guess: the correlative matcher's or the relocaliser's case
+FIELDALIGN_REJECTED = FIELDALIGN_BAD_POSE | FIELDALIGN_SINGULAR | FIELDALIGN_FEW | FIELDALIGN_DIVERGED | FIELDALIGN_WEAK
+_ALIGN_DOUBLES = ("trunc", "damp_t", "damp_r", "eps_t", "eps_r", "max_shift", "max_turn")
+_ALIGN_INTS = ("n_iter", "min_points", "min_permille")
 TILE = 64  # cells a side of the kernel's tile (lslam_grid.h GRID_T): the tests place rays on its seams
 
 
@@ -314,14 +320,27 @@ class DistanceField:
     revolution (``lslam_field_score``): how far the returns lie from the map's sources, and the robot's
     own clearance.  ``params``: mode (``DIST_OCC``: sources are the cells with L >= occ_min;
     ``DIST_NOT_FREE``: the cells with L > free_max and everything off the map), occ_min, free_max,
-    d_max (``lslam_dist_params``; defaults OCC, 85, -1, 64 cells) and trunc2, near2
-    (``lslam_fieldscore_params``; defaults 625, 4); off2 is d_max^2.  The grid's geometry and its
+    d_max (``lslam_dist_params``; defaults OCC, 85, -1, 64 cells), trunc2, near2
+    (``lslam_fieldscore_params``; defaults 625, 4); off2 is d_max^2; and trunc, damp_t, damp_r, eps_t,
+    eps_r, max_shift, max_turn, n_iter, min_points, min_permille (``lslam_fieldalign_params``; defaults
+    25 cells, 1, 100, 0.01 cell, 1e-4 rad, 200 mm, 0.1 rad, 10, 16, 500).  The grid's geometry and its
     device buffers are ``grid``'s, read in place::
 
         grid.step(xy, scan_chunk_off, chunk_pt_off, pose=lm)
         field.step()                                          # the field of the grid as it now stands
         field.score(xy, scan_chunk_off, chunk_pt_off, pose=lm)
         if field.clearance_mm().min() < 300.0: ...            # a robot is close to something
+
+    and the tracker's loop, a few Gauss-Newton steps in the field from the filter's pose
+    (``lslam_field_align``), with the exhaustive search kept for the robots that lost track::
+
+        grid.step(xy, scan_chunk_off, chunk_pt_off, pose=lm)  # the map from the last revolution
+        field.step()
+        field.align(next_xy, scan_chunk_off, chunk_pt_off, pose=lm, pose_out=lm.x)  # refines lm.x in place
+        lost = field.align_results()["flags"] & FIELDALIGN_REJECTED  # those robots kept their pose
+        if lost.any():                                        # GridLocalizer: the 41 x 21 x 21 window
+            loc.step(next_xy, scan_chunk_off, chunk_pt_off, grid=grid, pose=lm, write_back=True)
+        H, g = field.align_information()                      # the alignment's information, for a later fusion
 
     The field is recomputed whole by every ``step``: there is no incremental update after a
     revolution.  After an ``OccupancyGrid.recentre`` the next ``step`` computes the moved grid's field
@@ -334,16 +353,21 @@ class DistanceField:
         ctx, R, W = self.ctx, self.R, grid.W
         dk = {k: int(params.pop(k)) for k in ("mode", "occ_min", "free_max", "d_max") if k in params}
         sk = {k: int(params.pop(k)) for k in ("trunc2", "near2") if k in params}
+        ak = {k: float(params.pop(k)) for k in _ALIGN_DOUBLES if k in params}
+        ak.update({k: int(params.pop(k)) for k in _ALIGN_INTS if k in params})
         if params:
             raise TypeError("unknown parameters: %s" % ", ".join(sorted(params)))
         self.p = _lib.dist_params(**dk)
         self.q = _lib.fieldscore_params(off2=min(int(self.p.d_max) ** 2, 65025), **sk)
+        self.a = _lib.fieldalign_params(**ak)
         # (a range error of params surfaces here, before anything large is allocated)
         L = _lib.load()
         _lib.check(L.lslam_grid_distance(ctx.handle, C.byref(_lib.DistBatch()), C.byref(grid.p), C.byref(self.p)),
                    "lslam_grid_distance")
         _lib.check(L.lslam_field_score(ctx.handle, C.byref(_lib.FieldScoreBatch()), C.byref(grid.p), C.byref(self.q)),
                    "lslam_field_score")
+        _lib.check(L.lslam_field_align(ctx.handle, C.byref(_lib.FieldAlignBatch()), C.byref(grid.p), C.byref(self.a)),
+                   "lslam_field_align")
         self.d2 = ctx.empty((R, W, W), np.uint16)
         self.n_src = ctx.empty(R, np.int32)
         self.flags = ctx.empty(R, np.int32)
@@ -357,7 +381,8 @@ class DistanceField:
         self._off = ctx.empty(R + 1, np.int32)
         self._pose = ctx.empty((R, 3), np.float64)
         self._off_host = np.zeros(R + 1, np.int64)
-        self.steps = self.scores = 0
+        self.steps = self.scores = self.aligns = 0
+        self._align = None  # align's outputs, allocated by its first call
 
     def step(self, sync=True):
         """The field of the grid's device buffer as it now stands."""
@@ -388,6 +413,63 @@ class DistanceField:
         self.scores += 1
         if sync:
             ctx.sync()
+
+    def align(self, xy, scan_chunk_off=None, chunk_pt_off=None, pose=None, pose_out=None, sync=True):
+        """One revolution per robot aligned in the field of the last ``step`` (``lslam_field_align``): at
+        most ``n_iter`` damped Gauss-Newton steps from ``pose``, in one launch.  The argument forms are
+        those of ``score``.  ``pose_out``: a float64 ``DeviceArray`` [R, 3] that receives the aligned
+        pose, or the guess bit for bit where the flags reject it (``FIELDALIGN_REJECTED``); it may be
+        the array ``pose`` is read from, e.g. the filter's ``lm.x``.  None: a buffer of the field's own."""
+        if not self.steps:
+            raise ValueError("no step yet: the field has not been computed")
+        ctx, g, R = self.ctx, self.grid, self.R
+        if self._align is None:
+            rows = 33  # n_iter's upper end + 1: self.a.n_iter may change between calls
+            self._align = dict(pose_out=ctx.empty((R, 3), np.float64), trace=ctx.empty((R, rows, 5), np.float64),
+                               normal=ctx.empty((R, 10), np.int64), n_used=ctx.empty((R, 3), np.int32),
+                               iters=ctx.empty(R, np.int32), flags=ctx.empty(R, np.int32))
+        o = self._align
+        if pose_out is None:
+            pose_out = o["pose_out"]
+        if not isinstance(pose_out, DeviceArray) or pose_out.dtype != np.float64 or pose_out.nbytes < 24 * R:
+            raise ValueError("pose_out must be a float64 DeviceArray [n_robots, 3]")
+        dxy, doff, dpose = _stage_revolution(self, xy, scan_chunk_off, chunk_pt_off, pose)
+        b = _lib.FieldAlignBatch()
+        b.n_robots = R
+        b.xy, b.pt_off, b.pose, b.origin, b.d2 = dxy.addr, doff.addr, dpose.addr, g.origin.addr, self.d2.addr
+        b.pose_out, b.trace, b.normal = pose_out.addr, o["trace"].addr, o["normal"].addr
+        b.n_used, b.iters, b.flags = o["n_used"].addr, o["iters"].addr, o["flags"].addr
+        _lib.check(_lib.load().lslam_field_align(ctx.handle, C.byref(b), C.byref(g.p), C.byref(self.a)),
+                   "lslam_field_align")
+        self._align_out, self._align_rows = pose_out, int(self.a.n_iter) + 1
+        self.aligns += 1
+        if sync:
+            ctx.sync()
+
+    def align_results(self):
+        """The last align's pose_out [R, 3], trace [R, n_iter + 1, 5] (px, py, theta, cos, sin of every
+        evaluation, zeros beyond the last), normal [R, 10] int64 (the last evaluation's J^T J, J^T r and
+        r^2, times 2^20), n_used [R, 3] (points used at the first and at the last evaluation, valid
+        points in range), iters [R], flags [R] (``FIELDALIGN_*``)."""
+        if not self.aligns:
+            raise ValueError("no align yet")
+        o, E = self._align, self._align_rows
+        trace = o["trace"].download().reshape(-1)[:self.R * E * 5].reshape(self.R, E, 5)
+        return {"pose_out": self._align_out.download().reshape(-1)[:3 * self.R].reshape(self.R, 3), "trace": trace,
+                "normal": o["normal"].download(), "n_used": o["n_used"].download(), "iters": o["iters"].download(),
+                "flags": o["flags"].download()}
+
+    def align_information(self):
+        """The last align's Gauss-Newton information matrix H [R, 3, 3] = J^T J and vector g [R, 3] =
+        J^T r at its last evaluation, as float64 in cells and rad (without the damping): inv(H) times
+        the residual variance is the natural covariance of pose_out, the hook for fusing it."""
+        if not self.aligns:
+            raise ValueError("no align yet")
+        n = self._align["normal"].download().astype(np.float64) / float(2 ** 20)
+        H = np.empty((self.R, 3, 3))
+        for (i, j), k in {(0, 0): 0, (0, 1): 1, (0, 2): 2, (1, 1): 3, (1, 2): 4, (2, 2): 5}.items():
+            H[:, i, j] = H[:, j, i] = n[:, k]
+        return H, n[:, 6:9].copy()
 
     def results(self):
         """The last step's d2 [R, W, W] uint16, n_src [R], flags [R] (``DIST_EMPTY``)."""
