@@ -570,7 +570,10 @@ enum {
     LSLAM_FIELDALIGN_SINGULAR = 4,   /* a pivot of the solve is not finite and > 0, or the stepped pose is not finite: pose_out is pose */
     LSLAM_FIELDALIGN_FEW = 8,        /* an evaluation used fewer than min_points points: pose_out is pose */
     LSLAM_FIELDALIGN_DIVERGED = 16,  /* the pose left the guess by more than max_shift or max_turn: pose_out is pose */
-    LSLAM_FIELDALIGN_WEAK = 32       /* the last evaluation used less than min_permille of the valid points: pose_out is pose */
+    LSLAM_FIELDALIGN_WEAK = 32,      /* the last evaluation used less than min_permille of the valid points: pose_out is pose */
+    /* lslam_field_fuse only, in the same word: */
+    LSLAM_FIELDFUSE_OUTLIER = 64,    /* the innovation statistic exceeds nis_max: no update */
+    LSLAM_FIELDFUSE_BAD_COV = 128    /* P is not finite, or one of the fusion's three inverses fails its test: no update, nis = 0 */
 };
 
 /* Gauss-Newton alignment in the distance field (lslam_field_align), 72 bytes.  Lengths in cells unless
@@ -609,6 +612,34 @@ typedef struct lslam_fieldalign_batch {
     int32_t *iters;           /* [n_robots] steps taken */
     int32_t *flags;           /* [n_robots] LSLAM_FIELDALIGN_* */
 } lslam_fieldalign_batch;
+
+/* Field fusion (lslam_field_fuse), 48 bytes. */
+typedef struct lslam_fieldfuse_params {
+    double sigma_min;  /* floor on the residual standard deviation, cells; > 0, finite (0.5: the field resolves no less
+                          than half a cell) */
+    double r_scale;    /* factor on the noise variance; > 0, finite (1.0) */
+    double floor_t;    /* covariance floor on x and y, as a standard deviation in cells; > 0, finite (1 / sqrt(12): one
+                          cell's quantum, as lslam_map_fuse floors with one search quantum) */
+    double floor_r;    /* the same for the heading, rad; > 0, finite ((pi / 360) / sqrt(12): the matcher's heading quantum) */
+    double nis_max;    /* gate on the innovation statistic; > 0, +inf: no gate (16.27: the 99.9 % point of chi-square
+                          with 3 degrees of freedom) */
+    int64_t reserved;
+} lslam_fieldfuse_params;
+
+/* A field alignment fused into the filter, 152 bytes: the alignment's batch with its fields and rules as
+ * they are (a.pose is the filter's mean and the guess, a.pose_out the UPDATED mean), then the covariance
+ * and the measurement; all pointers DEVICE memory, all required. */
+typedef struct lslam_fieldfuse_batch {
+    lslam_fieldalign_batch a;
+    const double *P;          /* [n_robots][9] the filter's covariance, row-major, e.g. ukf_P */
+    double *P_out;            /* [n_robots][9] the updated covariance, or P bit for bit; MAY ALIAS P */
+    double *z;                /* [n_robots][3] the aligned pose, or the guess bit for bit; overlaps none of a.pose,
+                                 a.pose_out, P, P_out */
+    double *info;             /* [n_robots][9] the alignment's information matrix, mm and rad, row-major */
+    double *info_f;           /* [n_robots][9] the same with the covariance floor, the one that is fused */
+    double *s2;               /* [n_robots] the noise variance, squared cells */
+    double *nis;              /* [n_robots] the gated innovation statistic */
+} lslam_fieldfuse_batch;
 
 typedef struct lslam_ctx lslam_ctx;  /* opaque: device, stream, events, scratch */
 
@@ -661,6 +692,8 @@ int lslam_recentre_abi_sizes(int64_t *sizes, int n);
 int lslam_dist_abi_sizes(int64_t *sizes, int n);
 /* and for lslam_fieldalign_params, lslam_fieldalign_batch.  Writes min(n, 2) entries, returns 2. */
 int lslam_fieldalign_abi_sizes(int64_t *sizes, int n);
+/* and for lslam_fieldfuse_params, lslam_fieldfuse_batch.  Writes min(n, 2) entries, returns 2. */
+int lslam_fieldfuse_abi_sizes(int64_t *sizes, int n);
 /* per-kernel HIP-event timing on the ctx stream (kernel ids: LSLAM_K_*) */
 enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMARK = 3, LSLAM_K_UKF = 4,
        LSLAM_K_RNG = 5 /* parity-stream producer */, LSLAM_K_CONSENSUS = 6 /* per-chunk A4-A8 */,
@@ -701,6 +734,7 @@ int lslam_recentre_params_default(lslam_recentre_params *p);
 int lslam_dist_params_default(lslam_dist_params *p);
 int lslam_fieldscore_params_default(lslam_fieldscore_params *p);
 int lslam_fieldalign_params_default(lslam_fieldalign_params *p);
+int lslam_fieldfuse_params_default(lslam_fieldfuse_params *p);
 /* smallest e with RN(sqrt(e)) >= thr: (residual < thr) <=> (squared residual < cutoff) */
 double lslam_inlier_cutoff(double thr);
 /* MerweScaledSigmaPoints weights (filterpy _compute_weights) for n = 3 */
@@ -1139,6 +1173,54 @@ int lslam_field_score(lslam_ctx *ctx, const lslam_fieldscore_batch *b, const lsl
  * names the field), checked before the context is touched; n_robots == 0 does nothing. */
 int lslam_field_align(lslam_ctx *ctx, const lslam_fieldalign_batch *b, const lslam_grid_params *g,
                       const lslam_fieldalign_params *p);
+
+/* Field fusion: lslam_field_align as a measurement update of the filter.  The aligned pose is taken as a
+ * measurement z of the pose, with an information matrix built from the alignment's own normal equations,
+ * and (x, P) = (a.pose, P) is updated by a Kalman step in information form, gated on the innovation
+ * under the filter's own uncertainty.  The information form is deliberate: the undamped J^T J is singular
+ * in a corridor, so that a covariance R = inverse(Lambda) does not exist there; every quantity below is
+ * built from products and inverses of positive definite sums, and no two nearly equal matrices are
+ * subtracted.  All arithmetic is FP64, every operation rounded on its own.  Every element of a 3 x 3
+ * product is (t0 + t1) + t2.  "inverse" is the adjugate/determinant form of lslam_map_fuse step 7: the
+ * same nine entries p q - r s, det = (S00 A00 + S01 A10) + S02 A20, Si_ij = A_ij / det, and it passes iff
+ * S00 > 0 and A22 > 0 and det > 0 and det finite.  cell is g's, inv = 1.0 / cell.  Per robot r:
+ *   0-4. steps 0-4 of lslam_field_align, verbatim, with b->a, g and p, but that the pose which step 4
+ *      writes to pose_out goes to z[r] (for a rejected robot the guess, bit for bit).  trace, normal,
+ *      n_used, iters and flags are written as that call writes them.
+ *   5. if any of BAD_POSE, SINGULAR, FEW, DIVERGED, WEAK is set: info, info_f, s2 and nis are zeros,
+ *      pose_out and P_out are pose and P bit for bit (copied as 64-bit words: a NaN keeps its payload),
+ *      and the steps below are skipped.
+ *   6. noise.  n = n_last, sc = 2^-20, N = normal[r].  mean = ((double)N9 sc) / (double)n, or 0.0 if
+ *      n = 0; s2 = fmax(mean, sigma_min sigma_min) r_scale: the mean squared residual of the last
+ *      evaluation, in squared cells, floored and scaled.
+ *   7. the alignment's information, in mm and rad.  u = (inv, inv, 1.0).  For i <= j, k the index of
+ *      (xx, xy, xt, yy, yt, tt): Lambda_ij = ((((double)Nk sc) u_i) u_j) / s2, Lambda_ji = Lambda_ij.
+ *      There is no damping.  info[r] = Lambda.
+ *   8. floor.  ft = (floor_t cell)(floor_t cell), fr = floor_r floor_r, w = (1.0 / ft, 1.0 / ft,
+ *      1.0 / fr), taken once per call.  B = Lambda + diag(w) (three additions), Bi = inverse(B),
+ *      T = Lambda Bi, E_ij = T_ij w_j, Lambda_f = 0.5 (E_ij + E_ji): the information of the alignment's
+ *      covariance plus diag(ft, ft, fr), exact where a row of Lambda is zero.  info_f[r] = Lambda_f; if
+ *      B's inverse fails its test, info_f[r] is zeros.
+ *   9. prior.  Pi = inverse(P), M_ij = Pi_ij + Lambda_f_ij, Mi = inverse(M), Po_ij = 0.5 (Mi_ij + Mi_ji).
+ *      LSLAM_FIELDFUSE_BAD_COV iff some entry of P is not finite, or one of the three inverses fails its
+ *      test, or a diagonal entry of Po is not finite and > 0; then nis = 0.0 and steps 10-11 are skipped.
+ *   10. innovation and gate.  y_i = z_i - x_i, b = Lambda_f y, c = Po b, e = Pi c,
+ *      nis = (y0 e0 + y1 e1) + y2 e2: y^T inverse(P + R) y in product form.  LSLAM_FIELDFUSE_OUTLIER iff
+ *      not (nis <= nis_max).
+ *   11. update, iff neither BAD_COV nor OUTLIER: pose_out_i = x_i + c_i (no angle wrap), P_out = Po.
+ *      Otherwise pose_out and P_out are the input bits.  z, info, info_f, s2 and nis are reported as
+ *      computed.
+ * The field was drawn from the filter's own poses, so z is not independent of x: r_scale is the knob for
+ * that.  The residuals of points that share field cells are not independent either: the floors stand in
+ * for that.  z must not overlap a.pose, a.pose_out, P or P_out (LSLAM_ERR_ARG).  a.pose_out may be a.pose
+ * and P_out may be P: the one thread that writes a robot's pose_out and P_out has read its pose and P
+ * first.  The alignment is fieldalign_kernel's launch; steps 5-11 are one more launch on the same stream,
+ * one thread per robot (lslam_fieldfuse.h).  Runs on the context's main stream, after every earlier call.
+ * p is checked as lslam_field_align checks it.  Out-of-range parameters and missing pointers return
+ * LSLAM_ERR_ARG (the message names the field), checked before the context is touched; n_robots == 0
+ * does nothing. */
+int lslam_field_fuse(lslam_ctx *ctx, const lslam_fieldfuse_batch *b, const lslam_grid_params *g,
+                     const lslam_fieldalign_params *p, const lslam_fieldfuse_params *f);
 
 #ifdef __cplusplus
 }

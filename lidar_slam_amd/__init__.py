@@ -16,7 +16,8 @@ lidar_slam_amd.odometry.ScanMatcher / LidarOdometry (LiDAR-only odometry: wheel 
 lidar_slam_amd.mapping.OccupancyGrid (per-robot log-odds grids from the revolutions and the filter's poses;
 ``recentre`` rolls a grid under a robot that nears its edge),
 lidar_slam_amd.mapping.GridRayCaster (the grid read beam by beam: expected returns, beam classes, the dynamic-object mask),
-lidar_slam_amd.mapping.DistanceField (the grid's exact distance field: clearance, and a revolution's distance to the map),
+lidar_slam_amd.mapping.DistanceField (the grid's exact distance field: clearance, a revolution's distance to the map,
+its Gauss-Newton alignment there, and ``fuse``: that alignment as a gated Kalman update of the filter),
 lidar_slam_amd.localize.GridLocalizer (scan-to-map matching: the pose corrected against the robot's grid),
 lidar_slam_amd.localize.GridRelocalizer (global relocalisation: the pose found in the grid without a guess).
 """

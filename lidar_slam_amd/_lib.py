@@ -45,6 +45,7 @@ DIST_EMPTY = 1
 FIELD_BAD_POSE = 1
 (FIELDALIGN_BAD_POSE, FIELDALIGN_CONVERGED, FIELDALIGN_SINGULAR, FIELDALIGN_FEW, FIELDALIGN_DIVERGED,
  FIELDALIGN_WEAK) = 1, 2, 4, 8, 16, 32
+FIELDFUSE_OUTLIER, FIELDFUSE_BAD_COV = 64, 128
 
 
 class HIPLibraryError(RuntimeError):
@@ -196,6 +197,14 @@ class FieldAlignBatch(C.Structure):
                                    "iters", "flags")]
 
 
+class FieldFuseParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("sigma_min", "r_scale", "floor_t", "floor_r", "nis_max")] + [("reserved", C.c_int64)]
+
+
+class FieldFuseBatch(C.Structure):
+    _fields_ = [("a", FieldAlignBatch)] + [(n, _VP) for n in ("P", "P_out", "z", "info", "info_f", "s2", "nis")]
+
+
 assert C.sizeof(ChunkModel) == 112
 assert C.sizeof(LandmarkRec) == 56
 
@@ -218,6 +227,7 @@ EXPORTS = [
     "lslam_dist_abi_sizes", "lslam_dist_params_default", "lslam_fieldscore_params_default",
     "lslam_grid_distance", "lslam_field_score",
     "lslam_fieldalign_abi_sizes", "lslam_fieldalign_params_default", "lslam_field_align",
+    "lslam_fieldfuse_abi_sizes", "lslam_fieldfuse_params_default", "lslam_field_fuse",
 ]
 
 _lib = None
@@ -310,6 +320,9 @@ def load():
         "lslam_fieldalign_abi_sizes": ([P(i64), C.c_int], C.c_int),
         "lslam_fieldalign_params_default": ([P(FieldAlignParams)], C.c_int),
         "lslam_field_align": ([_VP, P(FieldAlignBatch), P(GridParams), P(FieldAlignParams)], C.c_int),
+        "lslam_fieldfuse_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_fieldfuse_params_default": ([P(FieldFuseParams)], C.c_int),
+        "lslam_field_fuse": ([_VP, P(FieldFuseBatch), P(GridParams), P(FieldAlignParams), P(FieldFuseParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -356,13 +369,16 @@ def _check_abi(L):
     L.lslam_dist_abi_sizes(got8, 4)
     got9 = (C.c_int64 * 2)()
     L.lslam_fieldalign_abi_sizes(got9, 2)
+    got10 = (C.c_int64 * 2)()
+    L.lslam_fieldfuse_abi_sizes(got10, 2)
     got = (list(got) + list(got2) + list(got3) + list(got4) + list(got5) + list(got6) + list(got7) + list(got8)
-           + list(got9))
+           + list(got9) + list(got10))
     want = want + [C.sizeof(GridParams), C.sizeof(GridBatch), C.sizeof(MapMatchParams), C.sizeof(MapMatchBatch),
                    C.sizeof(MapFuseParams), C.sizeof(MapFuseBatch), C.sizeof(RelocParams), C.sizeof(RelocBatch),
                    C.sizeof(RaycastParams), C.sizeof(RaycastBatch), C.sizeof(RecentreParams), C.sizeof(RecentreBatch),
                    C.sizeof(DistParams), C.sizeof(DistBatch), C.sizeof(FieldScoreParams), C.sizeof(FieldScoreBatch),
-                   C.sizeof(FieldAlignParams), C.sizeof(FieldAlignBatch)]
+                   C.sizeof(FieldAlignParams), C.sizeof(FieldAlignBatch), C.sizeof(FieldFuseParams),
+                   C.sizeof(FieldFuseBatch)]
     if list(got) != want:
         _err = HIPLibraryError("struct sizes differ between %s %s and the ctypes layouts %s"
                                % (LIB_PATH, list(got), want))
@@ -491,6 +507,14 @@ def fieldscore_params(**kw):
 def fieldalign_params(**kw):
     p = FieldAlignParams()
     load().lslam_fieldalign_params_default(C.byref(p))
+    for k, v in kw.items():
+        setattr(p, k, v)
+    return p
+
+
+def fieldfuse_params(**kw):
+    p = FieldFuseParams()
+    load().lslam_fieldfuse_params_default(C.byref(p))
     for k, v in kw.items():
         setattr(p, k, v)
     return p

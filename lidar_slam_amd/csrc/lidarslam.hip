@@ -14,7 +14,8 @@
 //   shift rule and in-place plan are lslam_recentre_plan.h, plain C++), lslam_dist.h (the distance
 //   field of the grid and its reader; the two 1-D passes are lslam_dist_core.h, plain C++),
 //   lslam_fieldalign.h (the Gauss-Newton alignment in the field; a point's terms and the 3 x 3 solve
-//   are lslam_fieldalign_core.h, plain C++);
+//   are lslam_fieldalign_core.h, plain C++), lslam_fieldfuse.h (the alignment fused into the filter; its
+//   3 x 3 algebra is lslam_fieldfuse_core.h, plain C++);
 // the host side is included at the foot:
 //   lslam_hazards.h  which waits a call's producer needs (plain C++, no HIP)
 //   lslam_ctx.h      lslam_ctx, its grow-only device buffers and timers, create / destroy,
@@ -3070,6 +3071,8 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
 #include "lslam_dist.h"
 // the alignment in the field, after its reader: the existing kernels keep their place
 #include "lslam_fieldalign.h"
+// the field fusion's kernel, a template: emitted behind every other, where it is first launched
+#include "lslam_fieldfuse.h"
 
 // ------------------------------------------------------------------------
 // host side: the context, then the launchers and entry points

@@ -422,6 +422,12 @@ int lslam_fieldalign_abi_sizes(int64_t *sizes, int n) {
     return 2;
 }
 
+int lslam_fieldfuse_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[2] = {(int64_t)sizeof(lslam_fieldfuse_params), (int64_t)sizeof(lslam_fieldfuse_batch)};
+    for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
+    return 2;
+}
+
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
     if (!c || (!dst && n)) return LSLAM_ERR_ARG;
     if (!n) return LSLAM_OK;
@@ -640,6 +646,17 @@ int lslam_fieldalign_params_default(lslam_fieldalign_params *p) {
     p->n_iter = 10;
     p->min_points = 16;    // three unknowns, with room for the outliers among them
     p->min_permille = 500;
+    return LSLAM_OK;
+}
+
+int lslam_fieldfuse_params_default(lslam_fieldfuse_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->sigma_min = 0.5;                             // cells: the field cannot resolve less than half a cell
+    p->r_scale = 1.0;
+    p->floor_t = 1.0 / sqrt(12.0);                  // cells: one cell's quantum, as lslam_map_fuse's search quantum
+    p->floor_r = (LS_PI / 360.0) / sqrt(12.0);      // rad: the matcher's heading quantum, so the two measurements floor alike
+    p->nis_max = 16.27;                             // the 99.9 % point of chi-square with 3 degrees of freedom
     return LSLAM_OK;
 }
 

@@ -1420,6 +1420,26 @@ static int launch_fieldalign(lslam_ctx *c, const lslam_fieldalign_batch *b, cons
     return LSLAM_OK;
 }
 
+// ---- field fusion (lslam_fieldfuse.h) ----
+
+static int fieldfuse_check_params(const lslam_fieldfuse_params *f) {
+    if (!f) return set_err(LSLAM_ERR_ARG, "fieldfuse: params is NULL");
+    if (!(f->sigma_min > 0) || !std::isfinite(f->sigma_min)) return set_err(LSLAM_ERR_ARG, "fieldfuse: sigma_min must be > 0 and finite");
+    if (!(f->r_scale > 0) || !std::isfinite(f->r_scale)) return set_err(LSLAM_ERR_ARG, "fieldfuse: r_scale must be > 0 and finite");
+    if (!(f->floor_t > 0) || !std::isfinite(f->floor_t)) return set_err(LSLAM_ERR_ARG, "fieldfuse: floor_t must be > 0 and finite");
+    if (!(f->floor_r > 0) || !std::isfinite(f->floor_r)) return set_err(LSLAM_ERR_ARG, "fieldfuse: floor_r must be > 0 and finite");
+    if (!(f->nis_max > 0)) return set_err(LSLAM_ERR_ARG, "fieldfuse: nis_max must be > 0 (+inf: no gate)");
+    return LSLAM_OK;
+}
+
+// true iff [a, a + na) and [b, b + nb) share a byte
+static bool fieldfuse_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    return x < y + nb && y < x + na;
+}
+
+// (launch_fieldfuse stands above lslam_field_fuse, behind every other launch: see there)
+
 // ---- express-scan codec (lslam_express.h) ----
 
 static inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
@@ -1783,6 +1803,73 @@ int lslam_field_align(lslam_ctx *c, const lslam_fieldalign_batch *b, const lslam
     if (b->n_robots == 0) return LSLAM_OK;
     HIPCHK(hipSetDevice(c->device));
     return launch_fieldalign(c, b, g, p);
+}
+
+// launch_fieldalign with pose_out := z, then one thread per robot for steps 5-11.  It stands here, behind
+// every other launch of the file, for fieldfuse_kernel's place in the code object: a kernel template is
+// emitted where it is first launched, and from here it lands behind the last scan_kernel instantiation,
+// so that no existing kernel moves against another.
+static int launch_fieldfuse(lslam_ctx *c, const lslam_fieldfuse_batch *b, const lslam_grid_params *g,
+                            const lslam_fieldalign_params *p, const lslam_fieldfuse_params *f) {
+    lslam_fieldalign_batch a = b->a;
+    a.pose_out = b->z;
+    int st = launch_fieldalign(c, &a, g, p);
+    if (st) return st;
+    FieldFuseArgs k;
+    memset(&k, 0, sizeof(k));
+    k.n_robots = b->a.n_robots;
+    k.pose = b->a.pose;
+    k.P = b->P;
+    k.z = b->z;
+    k.normal = b->a.normal;
+    k.n_used = b->a.n_used;
+    k.flags = b->a.flags;
+    k.pose_out = b->a.pose_out;
+    k.P_out = b->P_out;
+    k.info = b->info;
+    k.info_f = b->info_f;
+    k.s2 = b->s2;
+    k.nis = b->nis;
+    k.k = fieldfuse_consts(g->cell, f->sigma_min, f->r_scale, f->floor_t, f->floor_r, f->nis_max);
+    const size_t n = (size_t)b->a.n_robots;
+    const unsigned blocks = (unsigned)((n + FIELDFUSE_TPB - 1) / FIELDFUSE_TPB);
+    hipLaunchKernelGGL(fieldfuse_kernel<0>, dim3(blocks), dim3(FIELDFUSE_TPB), 0, c->stream, k);
+    HIPCHK(hipGetLastError());
+    c->hz.outs.add(b->a.pose_out, n * 24);
+    c->hz.outs.add(b->P_out, n * 72);
+    c->hz.outs.add(b->info, n * 72);
+    c->hz.outs.add(b->info_f, n * 72);
+    c->hz.outs.add(b->s2, n * 8);
+    c->hz.outs.add(b->nis, n * 8);
+    return LSLAM_OK;
+}
+
+// On the main stream, as lslam_field_align.
+int lslam_field_fuse(lslam_ctx *c, const lslam_fieldfuse_batch *b, const lslam_grid_params *g,
+                     const lslam_fieldalign_params *p, const lslam_fieldfuse_params *f) {
+    int st = grid_check_params(g);
+    if (st) return st;
+    if ((st = fieldalign_check_params(p))) return st;
+    if ((st = fieldfuse_check_params(f))) return st;
+    if (!b) return set_err(LSLAM_ERR_ARG, "fieldfuse: batch is NULL");
+    if (b->a.n_robots < 0) return set_err(LSLAM_ERR_ARG, "fieldfuse: negative n_robots");
+    if (b->a.n_robots > 0) {
+        const lslam_fieldalign_batch &a = b->a;
+        if (!a.xy || !a.pt_off || !a.pose || !a.origin || !a.d2 || !b->P)
+            return set_err(LSLAM_ERR_ARG, "fieldfuse: missing input (xy, pt_off, pose, origin, d2, P)");
+        if (!a.pose_out || !a.trace || !a.normal || !a.n_used || !a.iters || !a.flags || !b->P_out || !b->z || !b->info ||
+            !b->info_f || !b->s2 || !b->nis)
+            return set_err(LSLAM_ERR_ARG, "fieldfuse: missing output (pose_out, trace, normal, n_used, iters, flags, P_out, "
+                                          "z, info, info_f, s2, nis)");
+        const size_t n = (size_t)a.n_robots;
+        if (fieldfuse_overlap(b->z, n * 24, a.pose, n * 24) || fieldfuse_overlap(b->z, n * 24, a.pose_out, n * 24) ||
+            fieldfuse_overlap(b->z, n * 24, b->P, n * 72) || fieldfuse_overlap(b->z, n * 24, b->P_out, n * 72))
+            return set_err(LSLAM_ERR_ARG, "fieldfuse: z must not overlap pose, pose_out, P or P_out");
+    }
+    if (!c) return set_err(LSLAM_ERR_ARG, "fieldfuse: ctx is NULL");
+    if (b->a.n_robots == 0) return LSLAM_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return launch_fieldfuse(c, b, g, p, f);
 }
 
 // (the scratch is sized per call: a call in flight keeps the chunking it was launched with)

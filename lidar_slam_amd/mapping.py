@@ -34,6 +34,10 @@ FIELDALIGN_BAD_POSE, FIELDALIGN_CONVERGED, FIELDALIGN_SINGULAR = _lib.FIELDALIGN
 FIELDALIGN_FEW, FIELDALIGN_DIVERGED, FIELDALIGN_WEAK = _lib.FIELDALIGN_FEW, _lib.FIELDALIGN_DIVERGED, _lib.FIELDALIGN_WEAK
 # an alignment with one of these left pose_out as the guess: the correlative matcher's or the relocaliser's case
 FIELDALIGN_REJECTED = FIELDALIGN_BAD_POSE | FIELDALIGN_SINGULAR | FIELDALIGN_FEW | FIELDALIGN_DIVERGED | FIELDALIGN_WEAK
+FIELDFUSE_OUTLIER, FIELDFUSE_BAD_COV = _lib.FIELDFUSE_OUTLIER, _lib.FIELDFUSE_BAD_COV
+# a fusion with one of these left the filter's mean and covariance as they were
+FIELDFUSE_REJECTED = FIELDALIGN_REJECTED | FIELDFUSE_OUTLIER | FIELDFUSE_BAD_COV
+_FUSE_DOUBLES = ("sigma_min", "r_scale", "floor_t", "floor_r", "nis_max")
 _ALIGN_DOUBLES = ("trunc", "damp_t", "damp_r", "eps_t", "eps_r", "max_shift", "max_turn")
 _ALIGN_INTS = ("n_iter", "min_points", "min_permille")
 TILE = 64  # cells a side of the kernel's tile (lslam_grid.h GRID_T): the tests place rays on its seams
@@ -323,24 +327,28 @@ class DistanceField:
     d_max (``lslam_dist_params``; defaults OCC, 85, -1, 64 cells), trunc2, near2
     (``lslam_fieldscore_params``; defaults 625, 4); off2 is d_max^2; and trunc, damp_t, damp_r, eps_t,
     eps_r, max_shift, max_turn, n_iter, min_points, min_permille (``lslam_fieldalign_params``; defaults
-    25 cells, 1, 100, 0.01 cell, 1e-4 rad, 200 mm, 0.1 rad, 10, 16, 500).  The grid's geometry and its
-    device buffers are ``grid``'s, read in place::
+    25 cells, 1, 100, 0.01 cell, 1e-4 rad, 200 mm, 0.1 rad, 10, 16, 500); and sigma_min, r_scale, floor_t,
+    floor_r, nis_max (``lslam_fieldfuse_params``; defaults 0.5 cell, 1, 1 / sqrt(12) cell,
+    (pi / 360) / sqrt(12) rad, 16.27).  The grid's geometry and its device buffers are ``grid``'s, read in
+    place::
 
         grid.step(xy, scan_chunk_off, chunk_pt_off, pose=lm)
         field.step()                                          # the field of the grid as it now stands
         field.score(xy, scan_chunk_off, chunk_pt_off, pose=lm)
         if field.clearance_mm().min() < 300.0: ...            # a robot is close to something
 
-    and the tracker's loop, a few Gauss-Newton steps in the field from the filter's pose
-    (``lslam_field_align``), with the exhaustive search kept for the robots that lost track::
+    and the tracker's loop, a few Gauss-Newton steps in the field from the filter's pose fused into the
+    filter as a measurement (``lslam_field_fuse``), with the exhaustive search kept for the robots that
+    lost track::
 
         grid.step(xy, scan_chunk_off, chunk_pt_off, pose=lm)  # the map from the last revolution
         field.step()
-        field.align(next_xy, scan_chunk_off, chunk_pt_off, pose=lm, pose_out=lm.x)  # refines lm.x in place
-        lost = field.align_results()["flags"] & FIELDALIGN_REJECTED  # those robots kept their pose
+        field.fuse(next_xy, scan_chunk_off, chunk_pt_off, lm=lm)  # a gated Kalman update of lm.x and lm.P in place
+        lost = field.fuse_results()["flags"] & FIELDALIGN_REJECTED  # those robots kept their mean and covariance
         if lost.any():                                        # GridLocalizer: the 41 x 21 x 21 window
-            loc.step(next_xy, scan_chunk_off, chunk_pt_off, grid=grid, pose=lm, write_back=True)
-        H, g = field.align_information()                      # the alignment's information, for a later fusion
+            loc.fuse(next_xy, scan_chunk_off, chunk_pt_off, grid=grid, lm=lm)
+
+    (``field.align(.., pose=lm, pose_out=lm.x)`` is the same descent overwriting the mean alone.)
 
     The field is recomputed whole by every ``step``: there is no incremental update after a
     revolution.  After an ``OccupancyGrid.recentre`` the next ``step`` computes the moved grid's field
@@ -355,11 +363,13 @@ class DistanceField:
         sk = {k: int(params.pop(k)) for k in ("trunc2", "near2") if k in params}
         ak = {k: float(params.pop(k)) for k in _ALIGN_DOUBLES if k in params}
         ak.update({k: int(params.pop(k)) for k in _ALIGN_INTS if k in params})
+        fk = {k: float(params.pop(k)) for k in _FUSE_DOUBLES if k in params}
         if params:
             raise TypeError("unknown parameters: %s" % ", ".join(sorted(params)))
         self.p = _lib.dist_params(**dk)
         self.q = _lib.fieldscore_params(off2=min(int(self.p.d_max) ** 2, 65025), **sk)
         self.a = _lib.fieldalign_params(**ak)
+        self.f = _lib.fieldfuse_params(**fk)
         # (a range error of params surfaces here, before anything large is allocated)
         L = _lib.load()
         _lib.check(L.lslam_grid_distance(ctx.handle, C.byref(_lib.DistBatch()), C.byref(grid.p), C.byref(self.p)),
@@ -368,6 +378,8 @@ class DistanceField:
                    "lslam_field_score")
         _lib.check(L.lslam_field_align(ctx.handle, C.byref(_lib.FieldAlignBatch()), C.byref(grid.p), C.byref(self.a)),
                    "lslam_field_align")
+        _lib.check(L.lslam_field_fuse(ctx.handle, C.byref(_lib.FieldFuseBatch()), C.byref(grid.p), C.byref(self.a),
+                                      C.byref(self.f)), "lslam_field_fuse")
         self.d2 = ctx.empty((R, W, W), np.uint16)
         self.n_src = ctx.empty(R, np.int32)
         self.flags = ctx.empty(R, np.int32)
@@ -383,6 +395,8 @@ class DistanceField:
         self._off_host = np.zeros(R + 1, np.int64)
         self.steps = self.scores = self.aligns = 0
         self._align = None  # align's outputs, allocated by its first call
+        self._fuse = None   # fuse's own, likewise
+        self._fused = False  # the last align or fuse was a fuse
 
     def step(self, sync=True):
         """The field of the grid's device buffer as it now stands."""
@@ -423,12 +437,7 @@ class DistanceField:
         if not self.steps:
             raise ValueError("no step yet: the field has not been computed")
         ctx, g, R = self.ctx, self.grid, self.R
-        if self._align is None:
-            rows = 33  # n_iter's upper end + 1: self.a.n_iter may change between calls
-            self._align = dict(pose_out=ctx.empty((R, 3), np.float64), trace=ctx.empty((R, rows, 5), np.float64),
-                               normal=ctx.empty((R, 10), np.int64), n_used=ctx.empty((R, 3), np.int32),
-                               iters=ctx.empty(R, np.int32), flags=ctx.empty(R, np.int32))
-        o = self._align
+        o = self._align_buffers()
         if pose_out is None:
             pose_out = o["pose_out"]
         if not isinstance(pose_out, DeviceArray) or pose_out.dtype != np.float64 or pose_out.nbytes < 24 * R:
@@ -441,10 +450,79 @@ class DistanceField:
         b.n_used, b.iters, b.flags = o["n_used"].addr, o["iters"].addr, o["flags"].addr
         _lib.check(_lib.load().lslam_field_align(ctx.handle, C.byref(b), C.byref(g.p), C.byref(self.a)),
                    "lslam_field_align")
-        self._align_out, self._align_rows = pose_out, int(self.a.n_iter) + 1
+        self._align_out, self._align_rows, self._fused = pose_out, int(self.a.n_iter) + 1, False
         self.aligns += 1
         if sync:
             ctx.sync()
+
+    def _align_buffers(self):
+        ctx, R = self.ctx, self.R
+        if self._align is None:
+            rows = 33  # n_iter's upper end + 1: self.a.n_iter may change between calls
+            self._align = dict(pose_out=ctx.empty((R, 3), np.float64), trace=ctx.empty((R, rows, 5), np.float64),
+                               normal=ctx.empty((R, 10), np.int64), n_used=ctx.empty((R, 3), np.int32),
+                               iters=ctx.empty(R, np.int32), flags=ctx.empty(R, np.int32))
+        return self._align
+
+    def fuse(self, xy, scan_chunk_off=None, chunk_pt_off=None, lm=None, x=None, P=None, write_back=True, sync=True):
+        """The alignment of ``align`` fused into a filter (``lslam_field_fuse``): ``lm`` (a ``LandmarkMap``:
+        its ``x`` and ``P``), or ``x`` [R, 3] and ``P`` [R, 9] as float64 ``DeviceArray``s, in the argument
+        forms of ``GridLocalizer.fuse``.  The mean is the descent's guess; the aligned pose is a
+        measurement of it whose information comes from the alignment's own normal equations, and the
+        update is gated on the filter's uncertainty.  With ``write_back`` (the default) the updated mean
+        and covariance are written over them in place; otherwise they go to buffers of this object's,
+        and the filter is only read.  A robot with one of ``FIELDFUSE_REJECTED`` keeps the bits of its
+        mean and covariance."""
+        if not self.steps:
+            raise ValueError("no step yet: the field has not been computed")
+        ctx, g, R = self.ctx, self.grid, self.R
+        if lm is not None:
+            if x is not None or P is not None:
+                raise ValueError("give lm, or x and P")
+            if not isinstance(lm, LandmarkMap):
+                raise ValueError("lm must be a LandmarkMap")
+            if lm.R != R:
+                raise ValueError("the map holds %d robots, the grid %d" % (lm.R, R))
+            x, P = lm.x, lm.P
+        if not isinstance(x, DeviceArray) or not isinstance(P, DeviceArray):
+            raise ValueError("fuse needs the filter on the device: lm (a LandmarkMap), or x and P (DeviceArrays)")
+        if x.dtype != np.float64 or x.nbytes < 24 * R:
+            raise ValueError("device x must be float64 [n_robots, 3]")
+        if P.dtype != np.float64 or P.nbytes < 72 * R:
+            raise ValueError("device P must be float64 [n_robots, 9]")
+        o = self._align_buffers()
+        if self._fuse is None:
+            self._fuse = dict(P=ctx.empty((R, 9), np.float64), z=ctx.empty((R, 3), np.float64),
+                              info=ctx.empty((R, 9), np.float64), info_f=ctx.empty((R, 9), np.float64),
+                              s2=ctx.empty(R, np.float64), nis=ctx.empty(R, np.float64))
+        fo = self._fuse
+        dxy, doff, dpose = _stage_revolution(self, xy, scan_chunk_off, chunk_pt_off, x)
+        pose_out, P_out = (x, P) if write_back else (o["pose_out"], fo["P"])
+        b = _lib.FieldFuseBatch()
+        b.a.n_robots = R
+        b.a.xy, b.a.pt_off, b.a.pose, b.a.origin, b.a.d2 = dxy.addr, doff.addr, dpose.addr, g.origin.addr, self.d2.addr
+        b.a.pose_out, b.a.trace, b.a.normal = pose_out.addr, o["trace"].addr, o["normal"].addr
+        b.a.n_used, b.a.iters, b.a.flags = o["n_used"].addr, o["iters"].addr, o["flags"].addr
+        b.P, b.P_out, b.z = P.addr, P_out.addr, fo["z"].addr
+        b.info, b.info_f, b.s2, b.nis = fo["info"].addr, fo["info_f"].addr, fo["s2"].addr, fo["nis"].addr
+        _lib.check(_lib.load().lslam_field_fuse(ctx.handle, C.byref(b), C.byref(g.p), C.byref(self.a), C.byref(self.f)),
+                   "lslam_field_fuse")
+        self._align_out, self._align_rows, self._fused, self._P_out = pose_out, int(self.a.n_iter) + 1, True, P_out
+        self.aligns += 1
+        if sync:
+            ctx.sync()
+
+    def fuse_results(self):
+        """The last fuse's ``align_results`` (pose_out is the UPDATED mean) plus z [R, 3] (the aligned pose),
+        info and info_f [R, 3, 3] (the alignment's information in mm and rad, plain and floored), s2 [R]
+        (the noise variance, squared cells), nis [R] and P_out [R, 3, 3]; flags carry ``FIELDFUSE_*``."""
+        if not self._fused:
+            raise ValueError("no fuse yet")
+        out, fo, R = self.align_results(), self._fuse, self.R
+        out["z"], out["s2"], out["nis"] = fo["z"].download(), fo["s2"].download(), fo["nis"].download()
+        out["info"], out["info_f"] = fo["info"].download().reshape(R, 3, 3), fo["info_f"].download().reshape(R, 3, 3)
+        out["P_out"] = self._P_out.download().reshape(-1)[:9 * R].reshape(R, 3, 3)
+        return out
 
     def align_results(self):
         """The last align's pose_out [R, 3], trace [R, n_iter + 1, 5] (px, py, theta, cos, sin of every
@@ -462,7 +540,7 @@ class DistanceField:
     def align_information(self):
         """The last align's Gauss-Newton information matrix H [R, 3, 3] = J^T J and vector g [R, 3] =
         J^T r at its last evaluation, as float64 in cells and rad (without the damping): inv(H) times
-        the residual variance is the natural covariance of pose_out, the hook for fusing it."""
+        the residual variance is the natural covariance of pose_out; ``fuse`` is the call that fuses it."""
         if not self.aligns:
             raise ValueError("no align yet")
         n = self._align["normal"].download().astype(np.float64) / float(2 ** 20)
