@@ -349,40 +349,31 @@ def _check_abi(L):
                                % (LIB_PATH, ver, ABI_VERSION))
         raise _err
     _check_source(m.group(2))
-    got = (C.c_int64 * 9)()
-    L.lslam_abi_sizes(got, 9)
-    want = [C.sizeof(t) for t in (ChunkModel, LandmarkRec, RansacParams, UkfParams, ScanBatch, ExpressMeasures,
-                                  ExpressRevs, MatchParams, MatchBatch)]
-    got2 = (C.c_int64 * 2)()
-    L.lslam_grid_abi_sizes(got2, 2)
-    got3 = (C.c_int64 * 2)()
-    L.lslam_mapmatch_abi_sizes(got3, 2)
-    got4 = (C.c_int64 * 2)()
-    L.lslam_mapfuse_abi_sizes(got4, 2)
-    got5 = (C.c_int64 * 2)()
-    L.lslam_reloc_abi_sizes(got5, 2)
-    got6 = (C.c_int64 * 2)()
-    L.lslam_raycast_abi_sizes(got6, 2)
-    got7 = (C.c_int64 * 2)()
-    L.lslam_recentre_abi_sizes(got7, 2)
-    got8 = (C.c_int64 * 4)()
-    L.lslam_dist_abi_sizes(got8, 4)
-    got9 = (C.c_int64 * 2)()
-    L.lslam_fieldalign_abi_sizes(got9, 2)
-    got10 = (C.c_int64 * 2)()
-    L.lslam_fieldfuse_abi_sizes(got10, 2)
-    got = (list(got) + list(got2) + list(got3) + list(got4) + list(got5) + list(got6) + list(got7) + list(got8)
-           + list(got9) + list(got10))
-    want = want + [C.sizeof(GridParams), C.sizeof(GridBatch), C.sizeof(MapMatchParams), C.sizeof(MapMatchBatch),
-                   C.sizeof(MapFuseParams), C.sizeof(MapFuseBatch), C.sizeof(RelocParams), C.sizeof(RelocBatch),
-                   C.sizeof(RaycastParams), C.sizeof(RaycastBatch), C.sizeof(RecentreParams), C.sizeof(RecentreBatch),
-                   C.sizeof(DistParams), C.sizeof(DistBatch), C.sizeof(FieldScoreParams), C.sizeof(FieldScoreBatch),
-                   C.sizeof(FieldAlignParams), C.sizeof(FieldAlignBatch), C.sizeof(FieldFuseParams),
-                   C.sizeof(FieldFuseBatch)]
-    if list(got) != want:
-        _err = HIPLibraryError("struct sizes differ between %s %s and the ctypes layouts %s"
-                               % (LIB_PATH, list(got), want))
+    got, want = [], []
+    for sizes, structs in _ABI_SIZES:
+        buf = (C.c_int64 * len(structs))()
+        getattr(L, sizes)(buf, len(structs))
+        got += list(buf)
+        want += [C.sizeof(t) for t in structs]
+    if got != want:
+        _err = HIPLibraryError("struct sizes differ between %s %s and the ctypes layouts %s" % (LIB_PATH, got, want))
         raise _err
+
+
+# the exported sizes functions and the structs each reports, in its order
+_ABI_SIZES = [
+    ("lslam_abi_sizes", (ChunkModel, LandmarkRec, RansacParams, UkfParams, ScanBatch, ExpressMeasures, ExpressRevs,
+                         MatchParams, MatchBatch)),
+    ("lslam_grid_abi_sizes", (GridParams, GridBatch)),
+    ("lslam_mapmatch_abi_sizes", (MapMatchParams, MapMatchBatch)),
+    ("lslam_mapfuse_abi_sizes", (MapFuseParams, MapFuseBatch)),
+    ("lslam_reloc_abi_sizes", (RelocParams, RelocBatch)),
+    ("lslam_raycast_abi_sizes", (RaycastParams, RaycastBatch)),
+    ("lslam_recentre_abi_sizes", (RecentreParams, RecentreBatch)),
+    ("lslam_dist_abi_sizes", (DistParams, DistBatch, FieldScoreParams, FieldScoreBatch)),
+    ("lslam_fieldalign_abi_sizes", (FieldAlignParams, FieldAlignBatch)),
+    ("lslam_fieldfuse_abi_sizes", (FieldFuseParams, FieldFuseBatch)),
+]
 
 
 def _check_source(lib_hash, want=None):
@@ -412,12 +403,30 @@ def check(status, what=""):
     return status
 
 
-def ransac_params(**kw):
-    p = RansacParams()
-    load().lslam_ransac_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
+def _params_factory(name, struct):
+    """``name_params(**kw)``: the library's defaults for ``struct`` with the given fields set."""
+    def make(**kw):
+        p = struct()
+        getattr(load(), "lslam_%s_params_default" % name)(C.byref(p))
+        for k, v in kw.items():
+            setattr(p, k, v)
+        return p
+    make.__name__ = make.__qualname__ = name + "_params"
+    return make
+
+
+ransac_params = _params_factory("ransac", RansacParams)
+match_params = _params_factory("match", MatchParams)
+grid_params = _params_factory("grid", GridParams)
+mapmatch_params = _params_factory("mapmatch", MapMatchParams)
+mapfuse_params = _params_factory("mapfuse", MapFuseParams)
+reloc_params = _params_factory("reloc", RelocParams)
+raycast_params = _params_factory("raycast", RaycastParams)
+recentre_params = _params_factory("recentre", RecentreParams)
+dist_params = _params_factory("dist", DistParams)
+fieldscore_params = _params_factory("fieldscore", FieldScoreParams)
+fieldalign_params = _params_factory("fieldalign", FieldAlignParams)
+fieldfuse_params = _params_factory("fieldfuse", FieldFuseParams)
 
 
 def ukf_params(n_landmarks, **kw):
@@ -429,92 +438,4 @@ def ukf_params(n_landmarks, **kw):
                 p.Q[i] = float(q)
         else:
             setattr(p, k, v)
-    return p
-
-
-def match_params(**kw):
-    p = MatchParams()
-    load().lslam_match_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def grid_params(**kw):
-    p = GridParams()
-    load().lslam_grid_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def mapmatch_params(**kw):
-    p = MapMatchParams()
-    load().lslam_mapmatch_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def mapfuse_params(**kw):
-    p = MapFuseParams()
-    load().lslam_mapfuse_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def reloc_params(**kw):
-    p = RelocParams()
-    load().lslam_reloc_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def raycast_params(**kw):
-    p = RaycastParams()
-    load().lslam_raycast_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def recentre_params(**kw):
-    p = RecentreParams()
-    load().lslam_recentre_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def dist_params(**kw):
-    p = DistParams()
-    load().lslam_dist_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def fieldscore_params(**kw):
-    p = FieldScoreParams()
-    load().lslam_fieldscore_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def fieldalign_params(**kw):
-    p = FieldAlignParams()
-    load().lslam_fieldalign_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
-    return p
-
-
-def fieldfuse_params(**kw):
-    p = FieldFuseParams()
-    load().lslam_fieldfuse_params_default(C.byref(p))
-    for k, v in kw.items():
-        setattr(p, k, v)
     return p

@@ -20,8 +20,11 @@
 //   lslam_hazards.h  which waits a call's producer needs (plain C++, no HIP)
 //   lslam_ctx.h      lslam_ctx, its grow-only device buffers and timers, create / destroy,
 //                    the small ABI utilities
-//   lslam_launch.h   kernel arguments, LDS layouts, the launchers, run_split, the entry
-//                    points that launch kernels
+//   lslam_launch.h   the scan pipeline, the UKF and the express codec: kernel arguments, LDS
+//                    layouts, the launchers, run_split, their entry points
+//   lslam_launch_map.h  the map side (scan matcher ... field fusion): one entry frame, the
+//                    launchers, their entry points; included by lslam_launch.h, which says why
+//                    it stands where it does (the kernels' places in the code object)
 //
 // Execution model (lslam_scan_pipeline, parity mode):
 //   seed_kernel, cut_lane_kernel (seeding stream, fresh streams only) initial MT states;
@@ -3071,7 +3074,8 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
 #include "lslam_dist.h"
 // the alignment in the field, after its reader: the existing kernels keep their place
 #include "lslam_fieldalign.h"
-// the field fusion's kernel, a template: emitted behind every other, where it is first launched
+// the field fusion's kernel, a template: emitted behind every other (lslam_launch.h, at its include of
+// lslam_launch_map.h)
 #include "lslam_fieldfuse.h"
 
 // ------------------------------------------------------------------------

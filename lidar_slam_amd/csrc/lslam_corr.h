@@ -3,7 +3,7 @@
 // look-up grid G in LDS, a score per whole-cell shift and rotation of a revolution laid onto it, and
 // the winner of the score volume.  The definitions are the comments on lslam_scan_match and
 // lslam_map_match in include/lidarslam.h.  Here, once:
-//   CorrGeom                        the geometry of a search, filled by corr_geometry (lslam_launch.h)
+//   CorrGeom                        the geometry of a search, filled by corr_geometry (lslam_launch_map.h)
 //   match_grid_bytes ...            the LDS layout
 //   corr_smear_rows, _cols          occupancy -> G
 //   match_tile_task                 a thread's 16 candidates against its share of a tile's points

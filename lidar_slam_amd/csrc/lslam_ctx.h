@@ -1,6 +1,6 @@
 // Host side, part 1 (included by lidarslam.hip after the kernels): the context -- streams, events,
 // timers, grow-only device buffers -- its create / destroy, and the small ABI utilities (version,
-// errors, memory, copies, timers, parameter defaults).  The launchers are in lslam_launch.h.
+// errors, memory, copies, timers, parameter defaults).  The launchers are in lslam_launch.h and lslam_launch_map.h.
 #pragma once
 #include "lslam_hazards.h"
 

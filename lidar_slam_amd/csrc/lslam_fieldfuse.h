@@ -35,9 +35,8 @@ struct FieldFuseArgs {
     FieldFuseConsts k;
 };
 
-// (A template only for its place in the code object, as mapfuse_pick_kernel is: an instantiation is
-// emitted where it is first launched, and launch_fieldfuse stands behind every other launch of
-// lslam_launch.h, so this kernel is the code object's last and no existing kernel moves against another.)
+// (A template only for its place in the code object, as mapfuse_pick_kernel is: the code object's last.
+// The rule is at the include of lslam_launch_map.h in lslam_launch.h.)
 template <int kForm>
 __global__ __launch_bounds__(FIELDFUSE_TPB) void fieldfuse_kernel(const FieldFuseArgs a) {
     const int r = (int)blockIdx.x * FIELDFUSE_TPB + (int)threadIdx.x;

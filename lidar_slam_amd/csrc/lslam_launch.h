@@ -1,6 +1,7 @@
 // Host side, part 2 (included by lidarslam.hip after lslam_ctx.h): kernel arguments and LDS
 // layouts, the launchers, run_split (the pipeline call: the producer's waits come from
-// plan_producer, lslam_hazards.h) and the entry points that launch kernels.
+// plan_producer, lslam_hazards.h) and the entry points that launch kernels: the scan pipeline, the UKF
+// and the express codec.  The map side is lslam_launch_map.h, included below run_split.
 #pragma once
 #include <type_traits>
 
@@ -751,694 +752,16 @@ static int run_split(lslam_ctx *c, const lslam_scan_batch *b, const lslam_ransac
     return timer_end(c, LSLAM_K_PIPELINE);
 }
 
-
-// ---- the correlative search (lslam_corr.h): what the scan matcher and the scan-to-map matcher share ----
-
-// The range checks of both matchers' params; who: the errors' prefix, width_name: the width field's name.
-static int corr_check_params(const char *who, const char *width_name, double theta_step, int width, int smear, int k_trans,
-                             int k_theta) {
-    const std::string p = std::string(who) + ": ";
-    if (!(theta_step > 0) || !std::isfinite(theta_step)) return set_err(LSLAM_ERR_ARG, (p + "theta_step must be > 0").c_str());
-    if (width < 16 || width > 512 || (width & 1))
-        return set_err(LSLAM_ERR_ARG, (p + width_name + " must be even, in [16, 512]").c_str());
-    if (smear < 0 || smear > 2) return set_err(LSLAM_ERR_ARG, (p + "smear must be in [0, 2]").c_str());
-    if (k_trans < 0 || k_trans > 15) return set_err(LSLAM_ERR_ARG, (p + "k_trans must be in [0, 15]").c_str());
-    if (k_theta < 0 || k_theta > 31) return set_err(LSLAM_ERR_ARG, (p + "k_theta must be in [0, 31]").c_str());
-    return LSLAM_OK;
-}
-
-// The geometry of a search over n robots, the slice rule and the score volume (the caller's `scores`
-// or the context's scratch; vol = its bytes).  Slices: enough for two workgroups per CU (what the
-// LDS allows) when the robots alone do not give them, at most one per rotation; each slice rebuilds G.
-static int corr_geometry(lslam_ctx *c, const char *who, int n, double cell, double theta_step, int width, int smear,
-                         int k_trans, int k_theta, int32_t *scores, CorrGeom &g, size_t &vol) {
-    g.cell = cell;
-    g.inv = 1.0 / cell;
-    g.theta_step = theta_step;
-    g.n = n;
-    g.win_w = width;
-    g.half = width / 2;
-    g.smear = smear;
-    g.kt = k_trans;
-    g.kth = k_theta;
-    g.Nt = 2 * k_trans + 1;
-    g.Nth = 2 * k_theta + 1;
-    g.W = width + 2 * k_trans;
-    g.Sd = match_row_dwords(g.W);
-    const int64_t want = 2 * (int64_t)c->n_cus;
-    int64_t ns = (want + n - 1) / n;
-    ns = std::min<int64_t>(std::max<int64_t>(ns, 1), g.Nth);
-    g.per_slice = (int)((g.Nth + ns - 1) / ns);
-    g.n_slices = (g.Nth + g.per_slice - 1) / g.per_slice;
-    if ((int64_t)n * g.n_slices >= ((int64_t)1 << 31))
-        return set_err(LSLAM_ERR_UNSUPPORTED, (std::string(who) + ": too many robots in one call").c_str());
-    vol = (size_t)n * g.Nth * g.Nt * g.Nt * 4;
-    g.scores = scores;
-    if (!scores) {
-        int st = c->mscr.ensure(c, vol, (std::string(who) + " scores").c_str());
-        if (st) return st;
-        g.scores = c->mscr.as<int32_t>();
-    }
-    return LSLAM_OK;
-}
-
-// ---- scan matcher (lslam_match.h) ----
-
-static int match_check_params(const lslam_match_params *p) {
-    if (!p) return set_err(LSLAM_ERR_ARG, "match: params is NULL");
-    if (!(p->cell > 0) || !std::isfinite(p->cell)) return set_err(LSLAM_ERR_ARG, "match: cell must be > 0");
-    return corr_check_params("match", "grid_w", p->theta_step, p->grid_w, p->smear, p->k_trans, p->k_theta);
-}
-
-// match_search_kernel on a grid of (robots x rotation slices), then match_pick_kernel per robot.
-static int launch_match(lslam_ctx *c, const lslam_match_batch *b, const lslam_match_params *p,
-                        const lslam_ukf_params *u) {
-    MatchArgs k;
-    memset(&k, 0, sizeof(k));
-    k.b = *b;
-    size_t vol;
-    int st = corr_geometry(c, "match", b->n_scans, p->cell, p->theta_step, p->grid_w, p->smear, p->k_trans, p->k_theta,
-                           b->scores, k.g, vol);
-    if (st) return st;
-    k.write_u = (u && b->ukf_u) ? 1 : 0;
-    if (k.write_u) {
-        k.dt = u->dt;
-        k.wr = u->wheel_radius;
-        k.wb = u->wheel_base;
-    }
-    const int lds = match_lds_bytes(k.g.W, k.g.Sd, k.g.Nt);
-    static std::once_flag once;
-    std::call_once(once, [] { set_max_lds(match_search_kernel); });
-    if ((st = timer_begin(c, LSLAM_K_MATCH))) return st;
-    hipLaunchKernelGGL(match_search_kernel, dim3((unsigned)(k.g.n * k.g.n_slices)), dim3(MATCH_TPB), lds, c->stream, k);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(match_pick_kernel, dim3((unsigned)k.g.n), dim3(MATCH_PICK_TPB), 0, c->stream, k);
-    HIPCHK(hipGetLastError());
-    if ((st = timer_end(c, LSLAM_K_MATCH))) return st;
-    const size_t S = (size_t)b->n_scans;
-    c->hz.outs.add(b->delta, S * 24);
-    c->hz.outs.add(b->best, S * 16);
-    c->hz.outs.add(b->n_valid, S * 8);
-    c->hz.outs.add(b->flags, S * 4);
-    c->hz.outs.add(b->scores, vol);
-    if (k.write_u) c->hz.outs.add(b->ukf_u, S * 16);
-    return LSLAM_OK;
-}
-
-// ---- occupancy grid (lslam_grid.h) ----
-
-static int grid_check_params(const lslam_grid_params *p) {
-    if (!p) return set_err(LSLAM_ERR_ARG, "grid: params is NULL");
-    if (!(p->cell > 0) || !std::isfinite(p->cell)) return set_err(LSLAM_ERR_ARG, "grid: cell must be > 0");
-    if (!(p->max_range > 0) || !std::isfinite(p->max_range) || !(p->max_range / p->cell <= 4096.0))
-        return set_err(LSLAM_ERR_ARG, "grid: max_range must be > 0, finite and at most 4096 cells");
-    if (p->grid_w < 16 || p->grid_w > 2048) return set_err(LSLAM_ERR_ARG, "grid: grid_w must be in [16, 2048]");
-    if (p->l_hit < 1 || p->l_hit > 1024) return set_err(LSLAM_ERR_ARG, "grid: l_hit must be in [1, 1024]");
-    if (p->l_miss < -1024 || p->l_miss > -1) return set_err(LSLAM_ERR_ARG, "grid: l_miss must be in [-1024, -1]");
-    if (p->l_min < -32768 || p->l_min >= 0) return set_err(LSLAM_ERR_ARG, "grid: l_min must be in [-32768, -1]");
-    if (p->l_max <= 0 || p->l_max > 32767) return set_err(LSLAM_ERR_ARG, "grid: l_max must be in [1, 32767]");
-    return LSLAM_OK;
-}
-
-template <int T, int WAVE_RAY>
-static int launch_grid_form(lslam_ctx *c, GridArgs &k) {
-    k.ntile = (k.grid_w + T - 1) / T;
-    const int64_t blocks = (int64_t)k.b.n_robots * k.ntile * k.ntile;
-    if (blocks >= ((int64_t)1 << 31)) return set_err(LSLAM_ERR_UNSUPPORTED, "grid: too many robots in one call");
-    static std::once_flag once;
-    std::call_once(once, [] { set_max_lds(grid_update_kernel<T, WAVE_RAY>); });
-    hipLaunchKernelGGL((grid_update_kernel<T, WAVE_RAY>), dim3((unsigned)blocks), dim3(GRID_TPB), grid_lds_bytes(T),
-                       c->stream, k);
-    HIPCHK(hipGetLastError());
-    return LSLAM_OK;
-}
-
-// One workgroup per (robot, tile).  LSLAM_GRID_FORM (tools/gridbench.py) selects the forms that were
-// measured and dropped: "128l", "64w", "128w" (tile side; a lane or a wave per ray); default "64l".
-static int launch_grid(lslam_ctx *c, const lslam_grid_batch *b, const lslam_grid_params *p) {
-    GridArgs k;
-    memset(&k, 0, sizeof(k));
-    k.b = *b;
-    k.inv = 1.0 / p->cell;
-    k.max_r2 = p->max_range * p->max_range;
-    k.grid_w = p->grid_w;
-    k.l_hit = p->l_hit;
-    k.l_miss = p->l_miss;
-    k.l_min = p->l_min;
-    k.l_max = p->l_max;
-    k.vec = (p->grid_w % 8 == 0 && ((uintptr_t)b->logodds & 15) == 0) ? 1 : 0;
-    int T = GRID_T, wave_ray = GRID_WAVE_RAY;
-    if (const char *e = getenv("LSLAM_GRID_FORM")) {
-        if (atoi(e) == 64 || atoi(e) == 128) T = atoi(e);
-        if (strchr(e, 'l')) wave_ray = 0;
-        if (strchr(e, 'w')) wave_ray = 1;
-    }
-    int st = timer_begin(c, LSLAM_K_GRID);
-    if (st) return st;
-    if (T == 128) st = wave_ray ? launch_grid_form<128, 1>(c, k) : launch_grid_form<128, 0>(c, k);
-    else st = wave_ray ? launch_grid_form<64, 1>(c, k) : launch_grid_form<64, 0>(c, k);
-    if (st) return st;
-    if ((st = timer_end(c, LSLAM_K_GRID))) return st;
-    const size_t R = (size_t)b->n_robots;
-    c->hz.outs.add(b->logodds, R * (size_t)p->grid_w * (size_t)p->grid_w * 2);
-    c->hz.outs.add(b->rot, R * 16);
-    c->hz.outs.add(b->n_used, R * 8);
-    c->hz.outs.add(b->flags, R * 4);
-    return LSLAM_OK;
-}
-
-// ---- scan-to-map matcher (lslam_mapmatch.h) ----
-
-static int mapmatch_check_params(const lslam_mapmatch_params *m) {
-    if (!m) return set_err(LSLAM_ERR_ARG, "mapmatch: params is NULL");
-    int st = corr_check_params("mapmatch", "win_w", m->theta_step, m->win_w, m->smear, m->k_trans, m->k_theta);
-    if (st) return st;
-    if (m->occ_min < -32768 || m->occ_min > 32767)
-        return set_err(LSLAM_ERR_ARG, "mapmatch: occ_min must be in [-32768, 32767]");
-    if (m->min_permille < 0 || m->min_permille > 1000)
-        return set_err(LSLAM_ERR_ARG, "mapmatch: min_permille must be in [0, 1000]");
-    return LSLAM_OK;
-}
-
-// The matcher's pointers of a scan-to-map batch: 0 all there, 1 an input missing, 2 an output missing.
-// (The callers keep their own texts: lslam_map_fuse names more pointers.)
-static int mapmatch_missing(const lslam_mapmatch_batch *b) {
-    if (!b->xy || !b->pt_off || !b->pose || !b->origin || !b->logodds || !b->rot) return 1;
-    if (!b->pose_out || !b->delta || !b->best || !b->n_valid || !b->rot0 || !b->flags) return 2;
-    return 0;
-}
-
-// The kernels' arguments of a scan-to-map search (launch_mapmatch, launch_mapfuse and the fine stage
-// of launch_reloc); vol = the score volume's bytes.
-static int mapmatch_args(lslam_ctx *c, const lslam_mapmatch_batch *b, const lslam_grid_params *g,
-                         const lslam_mapmatch_params *m, MapMatchArgs &k, size_t &vol) {
-    memset(&k, 0, sizeof(k));
-    k.b = *b;
-    k.map_w = g->grid_w;
-    k.occ_min = m->occ_min;
-    k.min_permille = m->min_permille;
-    k.vec = (g->grid_w % 8 == 0 && ((uintptr_t)b->logodds & 15) == 0) ? 1 : 0;
-    // LSLAM_MAPMATCH_FORM=cell (tools/mapmatchbench.py): the lane-per-cell window load on every map
-    if (const char *e = getenv("LSLAM_MAPMATCH_FORM"))
-        if (!strcmp(e, "cell")) k.vec = 0;
-    return corr_geometry(c, "mapmatch", b->n_robots, g->cell, m->theta_step, m->win_w, m->smear, m->k_trans, m->k_theta,
-                         b->scores, k.g, vol);
-}
-
-static int launch_mapmatch_search(lslam_ctx *c, const MapMatchArgs &k) {
-    const int lds = mapmatch_lds_bytes(k.g.W, k.g.Sd, k.g.Nt);
-    static std::once_flag once;
-    std::call_once(once, [] { set_max_lds(mapmatch_search_kernel); });
-    hipLaunchKernelGGL(mapmatch_search_kernel, dim3((unsigned)(k.g.n * k.g.n_slices)), dim3(MATCH_TPB), lds, c->stream, k);
-    HIPCHK(hipGetLastError());
-    return LSLAM_OK;
-}
-
-// mapmatch_search_kernel on a grid of (robots x rotation slices), each slice reading the window and
-// rebuilding G, then mapmatch_pick_kernel per robot.
-static int launch_mapmatch_kernels(lslam_ctx *c, const MapMatchArgs &k) {
-    int st = launch_mapmatch_search(c, k);
-    if (st) return st;
-    hipLaunchKernelGGL(mapmatch_pick_kernel, dim3((unsigned)k.g.n), dim3(MATCH_PICK_TPB), 0, c->stream, k);
-    HIPCHK(hipGetLastError());
-    return LSLAM_OK;
-}
-
-// the matcher's outputs, for the hazard planner
-static void mapmatch_outs(lslam_ctx *c, const lslam_mapmatch_batch *b, size_t vol) {
-    const size_t R = (size_t)b->n_robots;
-    c->hz.outs.add(b->pose_out, R * 24);
-    c->hz.outs.add(b->delta, R * 24);
-    c->hz.outs.add(b->best, R * 16);
-    c->hz.outs.add(b->n_valid, R * 8);
-    c->hz.outs.add(b->rot0, R * 16);
-    c->hz.outs.add(b->flags, R * 4);
-    c->hz.outs.add(b->scores, vol);
-}
-
-static int launch_mapmatch(lslam_ctx *c, const lslam_mapmatch_batch *b, const lslam_grid_params *g,
-                           const lslam_mapmatch_params *m) {
-    MapMatchArgs k;
-    size_t vol;
-    int st = mapmatch_args(c, b, g, m, k, vol);
-    if (st) return st;
-    if ((st = timer_begin(c, LSLAM_K_MAPMATCH))) return st;
-    if ((st = launch_mapmatch_kernels(c, k))) return st;
-    if ((st = timer_end(c, LSLAM_K_MAPMATCH))) return st;
-    mapmatch_outs(c, b, vol);
-    return LSLAM_OK;
-}
-
-// ---- match fusion (lslam_mapfuse.h) ----
-
-static int mapfuse_check_params(const lslam_mapfuse_params *f) {
-    if (!f) return set_err(LSLAM_ERR_ARG, "mapfuse: params is NULL");
-    if (!(f->r_scale > 0) || !std::isfinite(f->r_scale))
-        return set_err(LSLAM_ERR_ARG, "mapfuse: r_scale must be > 0 and finite");
-    if (!(f->nis_max > 0)) return set_err(LSLAM_ERR_ARG, "mapfuse: nis_max must be > 0 (+inf: no gate)");
-    if (f->cut_permille < 0 || f->cut_permille > 999)
-        return set_err(LSLAM_ERR_ARG, "mapfuse: cut_permille must be in [0, 999]");
-    return LSLAM_OK;
-}
-
-// launch_mapmatch with mapfuse_pick_kernel in the place of mapmatch_pick_kernel.
-static int launch_mapfuse(lslam_ctx *c, const lslam_mapfuse_batch *b, const lslam_grid_params *g,
-                          const lslam_mapmatch_params *m, const lslam_mapfuse_params *f) {
-    MapFuseArgs k;
-    memset(&k, 0, sizeof(k));
-    size_t vol;
-    int st = mapmatch_args(c, &b->m, g, m, k.m, vol);
-    if (st) return st;
-    k.P = b->P;
-    k.P_out = b->P_out;
-    k.z = b->z;
-    k.Rm = b->Rm;
-    k.nis = b->nis;
-    k.moments = b->moments;
-    k.r_scale = f->r_scale;
-    k.nis_max = f->nis_max;
-    k.cut_permille = f->cut_permille;
-    if ((st = timer_begin(c, LSLAM_K_MAPFUSE))) return st;
-    if ((st = launch_mapmatch_search(c, k.m))) return st;
-    hipLaunchKernelGGL(mapfuse_pick_kernel<0>, dim3((unsigned)k.m.g.n), dim3(MATCH_PICK_TPB), 0, c->stream, k);
-    HIPCHK(hipGetLastError());
-    if ((st = timer_end(c, LSLAM_K_MAPFUSE))) return st;
-    const size_t R = (size_t)b->m.n_robots;
-    mapmatch_outs(c, &b->m, vol);
-    c->hz.outs.add(b->P_out, R * 72);
-    c->hz.outs.add(b->z, R * 24);
-    c->hz.outs.add(b->Rm, R * 72);
-    c->hz.outs.add(b->nis, R * 8);
-    c->hz.outs.add(b->moments, R * 80);
-    return LSLAM_OK;
-}
-
-// ---- relocalisation (lslam_reloc.h) ----
-
-static int reloc_check_params(const lslam_reloc_params *q, const lslam_grid_params *g, const lslam_mapmatch_params *m) {
-    if (!q) return set_err(LSLAM_ERR_ARG, "reloc: params is NULL");
-    if (!(q->head_step > 0) || !std::isfinite(q->head_step))
-        return set_err(LSLAM_ERR_ARG, "reloc: head_step must be > 0");
-    if (q->n_head < 4 || q->n_head > 1024) return set_err(LSLAM_ERR_ARG, "reloc: n_head must be in [4, 1024]");
-    if (q->factor != 2 && q->factor != 4 && q->factor != 8)
-        return set_err(LSLAM_ERR_ARG, "reloc: factor must be 2, 4 or 8");
-    if (g->grid_w % q->factor != 0 || g->grid_w / q->factor < 4 || g->grid_w / q->factor > 256)
-        return set_err(LSLAM_ERR_ARG, "reloc: factor must divide grid_w, with grid_w / factor in [4, 256]");
-    if (q->n_cand < 1 || q->n_cand > RELOC_KMAX) return set_err(LSLAM_ERR_ARG, "reloc: n_cand must be in [1, 16]");
-    if (q->ambig_permille < 0 || q->ambig_permille > 1000)
-        return set_err(LSLAM_ERR_ARG, "reloc: ambig_permille must be in [0, 1000]");
-    if (!(q->dup_mm >= 0)) return set_err(LSLAM_ERR_ARG, "reloc: dup_mm must be >= 0");
-    if (!(q->dup_rad >= 0)) return set_err(LSLAM_ERR_ARG, "reloc: dup_rad must be >= 0");
-    if (!(q->reset_sigma_xy > 0) || !std::isfinite(q->reset_sigma_xy))
-        return set_err(LSLAM_ERR_ARG, "reloc: reset_sigma_xy must be > 0 and finite");
-    if (!(q->reset_sigma_theta > 0) || !std::isfinite(q->reset_sigma_theta))
-        return set_err(LSLAM_ERR_ARG, "reloc: reset_sigma_theta must be > 0 and finite");
-    if (2 * m->k_trans < q->factor)
-        return set_err(LSLAM_ERR_ARG, "reloc: the fine window must cover a coarse cell: 2 k_trans >= factor");
-    if (!(2.0 * (double)m->k_theta * m->theta_step >= q->head_step))
-        return set_err(LSLAM_ERR_ARG, "reloc: the fine window must cover a heading step: 2 k_theta theta_step >= head_step");
-    return LSLAM_OK;
-}
-
-template <int FORM>
-static int launch_reloc_search(lslam_ctx *c, const RelocArgs &k, int nr) {
-    static std::once_flag once;
-    std::call_once(once, [] { set_max_lds(reloc_search_kernel<FORM>); });
-    hipLaunchKernelGGL(reloc_search_kernel<FORM>, dim3((unsigned)(nr * k.n_slices)), dim3(RELOC_TPB),
-                       reloc_lds_bytes(k.Wc, k.RW), c->stream, k);
-    HIPCHK(hipGetLastError());
-    return LSLAM_OK;
-}
-
-// The coarse stage in chunks of robots under the context's byte budget (search, peaks, the K best),
-// then K times the scan-to-map matcher (launch_mapmatch_kernels), rank j's arrays in the place of
-// the batch's, then the selection.  LSLAM_RELOC_FORM=add (tools/relocbench.py) selects the search
-// form that was measured and dropped.
-static int launch_reloc(lslam_ctx *c, const lslam_reloc_batch *b, const lslam_grid_params *g,
-                        const lslam_mapmatch_params *m, const lslam_reloc_params *q) {
-    const int R = b->n_robots, K = q->n_cand;
-    RelocArgs k;
-    memset(&k, 0, sizeof(k));
-    k.b = *b;
-    k.f = q->factor;
-    k.Wc = g->grid_w / q->factor;
-    k.cellc = g->cell * (double)q->factor;
-    k.invc = 1.0 / k.cellc;
-    k.head_step = q->head_step;
-    k.max_r2 = g->max_range * g->max_range;
-    k.dup_mm = q->dup_mm;
-    k.dup_rad = q->dup_rad;
-    k.pxy = q->reset_sigma_xy * q->reset_sigma_xy;
-    k.pth = q->reset_sigma_theta * q->reset_sigma_theta;
-    k.map_w = g->grid_w;
-    k.n_head = q->n_head;
-    k.K = K;
-    k.occ_min = m->occ_min;
-    k.ambig = q->ambig_permille;
-    k.nspan = (k.Wc + 31) / 32;
-    k.RW = reloc_row_dwords(k.Wc, k.nspan);
-    k.vec = (g->grid_w % 8 == 0 && ((uintptr_t)b->logodds & 15) == 0) ? 1 : 0;
-    if (const char *e = getenv("LSLAM_RELOC_FORM"))
-        if (!strcmp(e, "add")) k.form = 1;
-    const size_t cells = (size_t)k.n_head * k.Wc * k.Wc;
-    k.nbh = (k.Wc * k.Wc + RELOC_PEAK_BLOCK - 1) / RELOC_PEAK_BLOCK;
-    k.nblk = k.n_head * k.nbh;
-    const int nc = (int)std::min<size_t>((size_t)R, std::max<size_t>(1, c->reloc_budget / (cells * 4)));
-    const int64_t want = 2 * (int64_t)c->n_cus;
-    int64_t ns = (want + nc - 1) / nc;
-    ns = std::min<int64_t>(std::max<int64_t>(ns, 1), k.n_head);
-    k.per_slice = (int)((k.n_head + ns - 1) / ns);
-    k.n_slices = (k.n_head + k.per_slice - 1) / k.per_slice;
-    if ((int64_t)nc * k.nblk >= ((int64_t)1 << 31)) return set_err(LSLAM_ERR_UNSUPPORTED, "reloc: too many robots in one call");
-    const size_t keys_bytes = ((size_t)nc * k.nblk * K * 8 + 255) & ~(size_t)255;
-    int st = c->rscr.ensure(c, keys_bytes + (b->coarse_scores ? 0 : (size_t)nc * cells * 4), "reloc scratch");
-    if (st) return st;
-    k.keys = c->rscr.as<unsigned long long>();
-    // the fine stage's batch of rank 0: its scratch is grown here, before the timer and the first launch
-    lslam_mapmatch_batch mb;
-    memset(&mb, 0, sizeof(mb));
-    mb.n_robots = R;
-    mb.xy = b->xy;
-    mb.pt_off = b->pt_off;
-    mb.origin = b->origin;
-    mb.logodds = b->logodds;
-    mb.rot = b->rot;
-    MapMatchArgs mk;
-    size_t mvol;
-    if ((st = mapmatch_args(c, &mb, g, m, mk, mvol))) return st;
-    if ((st = timer_begin(c, LSLAM_K_RELOC))) return st;
-    for (int r0 = 0; r0 < R; r0 += nc) {
-        const int nr = std::min(nc, R - r0);
-        k.r0 = r0;
-        k.vol = b->coarse_scores ? b->coarse_scores + (size_t)r0 * cells : (int32_t *)(c->rscr.as<char>() + keys_bytes);
-        if ((st = k.form ? launch_reloc_search<1>(c, k, nr) : launch_reloc_search<0>(c, k, nr))) return st;
-        hipLaunchKernelGGL(reloc_peak_kernel, dim3((unsigned)(nr * k.nblk)), dim3(RELOC_PEAK_TPB), 0, c->stream, k);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(reloc_topk_kernel, dim3((unsigned)nr), dim3(RELOC_PEAK_TPB), 0, c->stream, k);
-        HIPCHK(hipGetLastError());
-    }
-    const size_t Rz = (size_t)R;
-    // LSLAM_RELOC_STAGES=coarse (tools/relocbench.py): the coarse stage alone; the fine outputs, result, flags
-    // and pose_out are not written
-    const char *stages = getenv("LSLAM_RELOC_STAGES");
-    if (stages && !strcmp(stages, "coarse")) return timer_end(c, LSLAM_K_RELOC);
-    for (int j = 0; j < K; j++) {
-        mb.pose = b->cand_pose + (size_t)j * Rz * 3;
-        mb.pose_out = b->fine_pose + (size_t)j * Rz * 3;
-        mb.delta = b->fine_delta + (size_t)j * Rz * 3;
-        mb.best = b->fine_best + (size_t)j * Rz * 4;
-        mb.n_valid = b->fine_nvalid + (size_t)j * Rz * 2;
-        mb.rot0 = b->fine_rot0 + (size_t)j * Rz * 2;
-        mb.flags = b->fine_flags + (size_t)j * Rz;
-        if ((st = mapmatch_args(c, &mb, g, m, mk, mvol))) return st;  // (the stream orders the reuse of its scratch)
-        if ((st = launch_mapmatch_kernels(c, mk))) return st;
-    }
-    hipLaunchKernelGGL(reloc_select_kernel, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, c->stream, k);
-    HIPCHK(hipGetLastError());
-    if ((st = timer_end(c, LSLAM_K_RELOC))) return st;
-    const size_t KR = (size_t)K * Rz;
-    c->hz.outs.add(b->n_occ, Rz * 4);
-    c->hz.outs.add(b->n_used, Rz * 4);
-    c->hz.outs.add(b->cand, KR * 16);
-    c->hz.outs.add(b->cand_pose, KR * 24);
-    c->hz.outs.add(b->fine_pose, KR * 24);
-    c->hz.outs.add(b->fine_delta, KR * 24);
-    c->hz.outs.add(b->fine_best, KR * 16);
-    c->hz.outs.add(b->fine_nvalid, KR * 8);
-    c->hz.outs.add(b->fine_rot0, KR * 16);
-    c->hz.outs.add(b->fine_flags, KR * 4);
-    c->hz.outs.add(b->result, Rz * 32);
-    c->hz.outs.add(b->flags, Rz * 4);
-    c->hz.outs.add(b->pose_out, Rz * 24);
-    c->hz.outs.add(b->P_out, Rz * 72);
-    c->hz.outs.add(b->coarse_scores, Rz * cells * 4);
-    return LSLAM_OK;
-}
-
-// ---- grid ray casting (lslam_raycast.h) ----
-
-static int raycast_check_params(const lslam_raycast_params *p) {
-    if (!p) return set_err(LSLAM_ERR_ARG, "raycast: params is NULL");
-    if (p->occ_min < -32768 || p->occ_min > 32767)
-        return set_err(LSLAM_ERR_ARG, "raycast: occ_min must be in [-32768, 32767]");
-    if (p->free_max < -32768 || p->free_max > 32766 || p->free_max >= p->occ_min)
-        return set_err(LSLAM_ERR_ARG, "raycast: free_max must be in [-32768, 32766] and below occ_min");
-    if (p->tol < 0 || p->tol > 64) return set_err(LSLAM_ERR_ARG, "raycast: tol must be in [0, 64]");
-    return LSLAM_OK;
-}
-
-template <int FORM>
-static int launch_raycast_form(lslam_ctx *c, const RaycastArgs &k, int lds) {
-    static std::once_flag once;
-    std::call_once(once, [] { set_max_lds(raycast_kernel<FORM>); });
-    hipLaunchKernelGGL(raycast_kernel<FORM>, dim3((unsigned)((int64_t)k.b.n_robots * k.n_slices)), dim3(RAYCAST_TPB), lds,
-                       c->stream, k);
-    HIPCHK(hipGetLastError());
-    return LSLAM_OK;
-}
-
-// One workgroup per (robot, slice of its points), by launch_mapmatch's rule: slices exist so that a
-// few robots still fill the chip.  The HBM form ships: in the bench room's grids it is the faster one
-// at 4096 robots.  LSLAM_RAYCAST_FORM=lds (tools/raycastbench.py, the tests) selects
-// the LDS form where the largest window's codes fit its budget.
-static int launch_raycast(lslam_ctx *c, const lslam_raycast_batch *b, const lslam_grid_params *g,
-                          const lslam_raycast_params *p) {
-    RaycastArgs k;
-    memset(&k, 0, sizeof(k));
-    k.b = *b;
-    k.inv = 1.0 / g->cell;
-    k.max_r2 = g->max_range * g->max_range;
-    k.far = g->max_range + 2.0 * g->cell;
-    k.grid_w = g->grid_w;
-    k.Rc = (int)floor(g->max_range * k.inv);
-    k.occ_min = p->occ_min;
-    k.free_max = p->free_max;
-    k.tol = p->tol;
-    k.vec = (g->grid_w % 8 == 0 && ((uintptr_t)b->logodds & 15) == 0) ? 1 : 0;
-    const int win = raycast_window(k.Rc, k.grid_w);
-    k.Sd = raycast_row_dwords(win);
-    int hbm = 1;
-    if (const char *e = getenv("LSLAM_RAYCAST_FORM"))
-        if (!strcmp(e, "lds") && raycast_lds_bytes(win) <= RAYCAST_LDS_BUDGET) hbm = 0;
-    const int64_t n = b->n_robots, want = 2 * (int64_t)c->n_cus;
-    k.n_slices = (int)std::min<int64_t>(std::max<int64_t>((want + n - 1) / n, 1), RAYCAST_MAX_SLICES);
-    if (n * k.n_slices >= ((int64_t)1 << 31)) return set_err(LSLAM_ERR_UNSUPPORTED, "raycast: too many robots in one call");
-    int st = timer_begin(c, LSLAM_K_RAYCAST);
-    if (st) return st;
-    HIPCHK(hipMemsetAsync(b->counts, 0, (size_t)n * 32, c->stream));
-    st = hbm ? launch_raycast_form<1>(c, k, 32) : launch_raycast_form<0>(c, k, raycast_lds_bytes(win));
-    if (st) return st;
-    if ((st = timer_end(c, LSLAM_K_RAYCAST))) return st;
-    // (cls and stop are as long as pt_off, on the device, says: per-point outputs that no producer reads)
-    c->hz.outs.add(b->counts, (size_t)n * 32);
-    c->hz.outs.add(b->rot, (size_t)n * 16);
-    c->hz.outs.add(b->flags, (size_t)n * 4);
-    return LSLAM_OK;
-}
-
-// ---- grid recentre (lslam_recentre.h) ----
-
-static int recentre_check_params(const lslam_recentre_params *p, const lslam_grid_params *g) {
-    if (!p) return set_err(LSLAM_ERR_ARG, "recentre: params is NULL");
-    if (p->margin < 0 || p->margin > g->grid_w / 2)
-        return set_err(LSLAM_ERR_ARG, "recentre: margin must be in [0, grid_w / 2]");
-    if (p->quantum < 1 || p->quantum > 64) return set_err(LSLAM_ERR_ARG, "recentre: quantum must be in [1, 64]");
-    return LSLAM_OK;
-}
-
-// One workgroup per robot (two on one robot would race: lslam_recentre.h).  With grid_w and quantum
-// multiples of 8 every shift lies on 16-byte groups and the instantiation without the lane-per-cell
-// path, and without its LDS, is launched.
-static int launch_recentre(lslam_ctx *c, const lslam_recentre_batch *b, const lslam_grid_params *g,
-                           const lslam_recentre_params *p) {
-    RecentreArgs k;
-    memset(&k, 0, sizeof(k));
-    k.b = *b;
-    k.cell = g->cell;
-    k.inv = 1.0 / g->cell;
-    k.grid_w = g->grid_w;
-    k.margin = p->margin;
-    k.quantum = p->quantum;
-    k.band_rows = recentre_band_rows(g->grid_w);
-    k.vec = (g->grid_w % 8 == 0 && ((uintptr_t)b->logodds & 15) == 0) ? 1 : 0;
-    if (b->n_robots > (1 << 30)) return set_err(LSLAM_ERR_UNSUPPORTED, "recentre: too many robots in one call");
-    int st = timer_begin(c, LSLAM_K_RECENTRE);
-    if (st) return st;
-    if (k.vec && p->quantum % 8 == 0)
-        hipLaunchKernelGGL(recentre_kernel<0>, dim3((unsigned)recentre_blocks(b->n_robots)), dim3(RECENTRE_TPB), 0, c->stream, k);
-    else
-        hipLaunchKernelGGL(recentre_kernel<1>, dim3((unsigned)recentre_blocks(b->n_robots)), dim3(RECENTRE_TPB), 0, c->stream, k);
-    HIPCHK(hipGetLastError());
-    if ((st = timer_end(c, LSLAM_K_RECENTRE))) return st;
-    const size_t R = (size_t)b->n_robots;
-    c->hz.outs.add(b->logodds, R * (size_t)g->grid_w * (size_t)g->grid_w * 2);
-    c->hz.outs.add(b->origin, R * 16);
-    c->hz.outs.add(b->shift, R * 8);
-    c->hz.outs.add(b->flags, R * 4);
-    return LSLAM_OK;
-}
-
-// ---- distance field and its read (lslam_dist.h) ----
-
-static int dist_check_params(const lslam_dist_params *p) {
-    if (!p) return set_err(LSLAM_ERR_ARG, "dist: params is NULL");
-    if (p->mode != LSLAM_DIST_OCC && p->mode != LSLAM_DIST_NOT_FREE)
-        return set_err(LSLAM_ERR_ARG, "dist: mode must be LSLAM_DIST_OCC or LSLAM_DIST_NOT_FREE");
-    if (p->occ_min < -32768 || p->occ_min > 32767) return set_err(LSLAM_ERR_ARG, "dist: occ_min must be in [-32768, 32767]");
-    if (p->free_max < -32768 || p->free_max > 32767)
-        return set_err(LSLAM_ERR_ARG, "dist: free_max must be in [-32768, 32767]");
-    if (p->d_max < 1 || p->d_max > DIST_D_MAX) return set_err(LSLAM_ERR_ARG, "dist: d_max must be in [1, 255]");
-    return LSLAM_OK;
-}
-
-// The band of rows of a workgroup: all of a robot's rows when the robots alone fill the chip, else so
-// many bands that there are two workgroups to a CU (at most DIST_MAX_SLICES per robot), in whole
-// groups of DIST_NW rows; then shrunk until the workgroup's LDS leaves room for two on a CU, or at
-// least fits one.  0: not even a band of DIST_NW rows fits.
-static int dist_band_rows(int W, int hal, int64_t n_robots, int n_cus) {
-    const int64_t want = std::min<int64_t>(std::max<int64_t>((2 * (int64_t)n_cus + n_robots - 1) / n_robots, 1), DIST_MAX_SLICES);
-    int band = (int)((W + want - 1) / want);
-    band = (band + DIST_NW - 1) / DIST_NW * DIST_NW;
-    while (band > DIST_NW && dist_lds_bytes(W, dist_blocks(W, band, hal)) > DIST_LDS_TWO) band -= DIST_NW;
-    if (dist_lds_bytes(W, dist_blocks(W, band, hal)) <= DIST_LDS_TWO) return band;
-    // (no band leaves room for two: the largest that fits one)
-    band = (int)((W + want - 1) / want);
-    band = (band + DIST_NW - 1) / DIST_NW * DIST_NW;
-    while (band > DIST_NW && dist_lds_bytes(W, dist_blocks(W, band, hal)) > DIST_LDS_MAX) band -= DIST_NW;
-    return dist_lds_bytes(W, dist_blocks(W, band, hal)) <= DIST_LDS_MAX ? band : 0;
-}
-
-static int launch_dist(lslam_ctx *c, const lslam_dist_batch *b, const lslam_grid_params *g, const lslam_dist_params *p) {
-    static std::once_flag once;
-    std::call_once(once, [] {
-        set_max_lds(dist_kernel<8>);
-        set_max_lds(dist_kernel<1>);
-    });
-    DistArgs k;
-    memset(&k, 0, sizeof(k));
-    k.b = *b;
-    k.grid_w = g->grid_w;
-    k.d_max = p->d_max;
-    k.not_free = p->mode == LSLAM_DIST_NOT_FREE ? 1 : 0;
-    k.thr = k.not_free ? p->free_max + 1 : p->occ_min;
-    k.hal = std::min(p->d_max, g->grid_w) - 1;
-    k.band = dist_band_rows(k.grid_w, k.hal, b->n_robots, c->n_cus);
-    if (!k.band) return set_err(LSLAM_ERR_UNSUPPORTED, "dist: the bitmap of 2 d_max rows of this grid_w does not fit LDS");
-    k.n_slices = (k.grid_w + k.band - 1) / k.band;
-    k.nblk = dist_blocks(k.grid_w, k.band, k.hal);
-    const int lds = dist_lds_bytes(k.grid_w, k.nblk);
-    const int64_t n = b->n_robots;
-    if (n * k.n_slices >= ((int64_t)1 << 31)) return set_err(LSLAM_ERR_UNSUPPORTED, "dist: too many robots in one call");
-    const bool vec = g->grid_w % 8 == 0 && (((uintptr_t)b->logodds | (uintptr_t)b->d2) & 15) == 0;
-    HIPCHK(hipMemsetAsync(b->n_src, 0, (size_t)n * 4, c->stream));
-    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)b->flags, LSLAM_DIST_EMPTY, (size_t)n, c->stream));
-    if (vec) hipLaunchKernelGGL(dist_kernel<8>, dim3((unsigned)(n * k.n_slices)), dim3(DIST_TPB), lds, c->stream, k);
-    else hipLaunchKernelGGL(dist_kernel<1>, dim3((unsigned)(n * k.n_slices)), dim3(DIST_TPB), lds, c->stream, k);
-    HIPCHK(hipGetLastError());
-    c->hz.outs.add(b->d2, (size_t)n * (size_t)g->grid_w * (size_t)g->grid_w * 2);
-    c->hz.outs.add(b->n_src, (size_t)n * 4);
-    c->hz.outs.add(b->flags, (size_t)n * 4);
-    return LSLAM_OK;
-}
-
-static int fieldscore_check_params(const lslam_fieldscore_params *p) {
-    if (!p) return set_err(LSLAM_ERR_ARG, "fieldscore: params is NULL");
-    if (p->trunc2 < 1 || p->trunc2 > 65025) return set_err(LSLAM_ERR_ARG, "fieldscore: trunc2 must be in [1, 65025]");
-    if (p->near2 < 0 || p->near2 > 65025) return set_err(LSLAM_ERR_ARG, "fieldscore: near2 must be in [0, 65025]");
-    if (p->off2 < 0 || p->off2 > 65025) return set_err(LSLAM_ERR_ARG, "fieldscore: off2 must be in [0, 65025]");
-    return LSLAM_OK;
-}
-
-// One workgroup per (robot, slice of its points), by launch_raycast's rule.
-static int launch_fieldscore(lslam_ctx *c, const lslam_fieldscore_batch *b, const lslam_grid_params *g,
-                             const lslam_fieldscore_params *p) {
-    FieldScoreArgs k;
-    memset(&k, 0, sizeof(k));
-    k.b = *b;
-    k.inv = 1.0 / g->cell;
-    k.max_r2 = g->max_range * g->max_range;
-    k.grid_w = g->grid_w;
-    k.trunc2 = p->trunc2;
-    k.near2 = p->near2;
-    k.off2 = p->off2;
-    const int64_t n = b->n_robots, want = 2 * (int64_t)c->n_cus;
-    k.n_slices = (int)std::min<int64_t>(std::max<int64_t>((want + n - 1) / n, 1), FIELDSCORE_MAX_SLICES);
-    if (n * k.n_slices >= ((int64_t)1 << 31)) return set_err(LSLAM_ERR_UNSUPPORTED, "fieldscore: too many robots in one call");
-    HIPCHK(hipMemsetAsync(b->stats, 0, (size_t)n * 32, c->stream));
-    hipLaunchKernelGGL(fieldscore_kernel, dim3((unsigned)(n * k.n_slices)), dim3(FIELDSCORE_TPB), 0, c->stream, k);
-    HIPCHK(hipGetLastError());
-    c->hz.outs.add(b->rot, (size_t)n * 16);
-    c->hz.outs.add(b->stats, (size_t)n * 32);
-    c->hz.outs.add(b->clear2, (size_t)n * 4);
-    c->hz.outs.add(b->flags, (size_t)n * 4);
-    return LSLAM_OK;
-}
-
-// ---- alignment in the field (lslam_fieldalign.h) ----
-
-static int fieldalign_check_params(const lslam_fieldalign_params *p) {
-    if (!p) return set_err(LSLAM_ERR_ARG, "fieldalign: params is NULL");
-    if (!(p->trunc >= 0.0 && p->trunc <= 255.0)) return set_err(LSLAM_ERR_ARG, "fieldalign: trunc must be in [0, 255]");
-    if (!(p->damp_t >= 0.0) || !std::isfinite(p->damp_t)) return set_err(LSLAM_ERR_ARG, "fieldalign: damp_t must be >= 0 and finite");
-    if (!(p->damp_r >= 0.0) || !std::isfinite(p->damp_r)) return set_err(LSLAM_ERR_ARG, "fieldalign: damp_r must be >= 0 and finite");
-    if (!(p->eps_t >= 0.0) || !std::isfinite(p->eps_t)) return set_err(LSLAM_ERR_ARG, "fieldalign: eps_t must be >= 0 and finite");
-    if (!(p->eps_r >= 0.0) || !std::isfinite(p->eps_r)) return set_err(LSLAM_ERR_ARG, "fieldalign: eps_r must be >= 0 and finite");
-    if (!(p->max_shift >= 0.0)) return set_err(LSLAM_ERR_ARG, "fieldalign: max_shift must be >= 0");
-    if (!(p->max_turn >= 0.0)) return set_err(LSLAM_ERR_ARG, "fieldalign: max_turn must be >= 0");
-    if (p->n_iter < 1 || p->n_iter > FIELDALIGN_MAX_ITER) return set_err(LSLAM_ERR_ARG, "fieldalign: n_iter must be in [1, 32]");
-    if (p->min_points < 0) return set_err(LSLAM_ERR_ARG, "fieldalign: min_points must be >= 0");
-    if (p->min_permille < 0 || p->min_permille > 1000) return set_err(LSLAM_ERR_ARG, "fieldalign: min_permille must be in [0, 1000]");
-    return LSLAM_OK;
-}
-
-// One wave per robot, FIELDALIGN_RPB robots to a workgroup.
-static int launch_fieldalign(lslam_ctx *c, const lslam_fieldalign_batch *b, const lslam_grid_params *g,
-                             const lslam_fieldalign_params *p) {
-    FieldAlignArgs k;
-    memset(&k, 0, sizeof(k));
-    k.b = *b;
-    k.p = *p;
-    k.cell = g->cell;
-    k.inv = 1.0 / g->cell;
-    k.max_r2 = g->max_range * g->max_range;
-    k.grid_w = g->grid_w;
-    const size_t n = (size_t)b->n_robots, rows = (size_t)p->n_iter + 1;
-    // (pose_out is written for every robot; the rest is zeros where the kernel writes nothing)
-    HIPCHK(hipMemsetAsync(b->trace, 0, n * rows * 40, c->stream));
-    HIPCHK(hipMemsetAsync(b->normal, 0, n * 80, c->stream));
-    HIPCHK(hipMemsetAsync(b->n_used, 0, n * 12, c->stream));
-    HIPCHK(hipMemsetAsync(b->iters, 0, n * 4, c->stream));
-    const unsigned blocks = (unsigned)((n + FIELDALIGN_RPB - 1) / FIELDALIGN_RPB);
-    hipLaunchKernelGGL(fieldalign_kernel, dim3(blocks), dim3(FIELDALIGN_TPB), 0, c->stream, k);
-    HIPCHK(hipGetLastError());
-    c->hz.outs.add(b->pose_out, n * 24);
-    c->hz.outs.add(b->trace, n * rows * 40);
-    c->hz.outs.add(b->normal, n * 80);
-    c->hz.outs.add(b->n_used, n * 12);
-    c->hz.outs.add(b->iters, n * 4);
-    c->hz.outs.add(b->flags, n * 4);
-    return LSLAM_OK;
-}
-
-// ---- field fusion (lslam_fieldfuse.h) ----
-
-static int fieldfuse_check_params(const lslam_fieldfuse_params *f) {
-    if (!f) return set_err(LSLAM_ERR_ARG, "fieldfuse: params is NULL");
-    if (!(f->sigma_min > 0) || !std::isfinite(f->sigma_min)) return set_err(LSLAM_ERR_ARG, "fieldfuse: sigma_min must be > 0 and finite");
-    if (!(f->r_scale > 0) || !std::isfinite(f->r_scale)) return set_err(LSLAM_ERR_ARG, "fieldfuse: r_scale must be > 0 and finite");
-    if (!(f->floor_t > 0) || !std::isfinite(f->floor_t)) return set_err(LSLAM_ERR_ARG, "fieldfuse: floor_t must be > 0 and finite");
-    if (!(f->floor_r > 0) || !std::isfinite(f->floor_r)) return set_err(LSLAM_ERR_ARG, "fieldfuse: floor_r must be > 0 and finite");
-    if (!(f->nis_max > 0)) return set_err(LSLAM_ERR_ARG, "fieldfuse: nis_max must be > 0 (+inf: no gate)");
-    return LSLAM_OK;
-}
-
-// true iff [a, a + na) and [b, b + nb) share a byte
-static bool fieldfuse_overlap(const void *a, size_t na, const void *b, size_t nb) {
-    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-    return x < y + nb && y < x + na;
-}
-
-// (launch_fieldfuse stands above lslam_field_fuse, behind every other launch: see there)
+// The map side: its launchers and entry points.  Why here, between the launchers above and the entry
+// points below: a kernel template is emitted into the code object where the translation unit first
+// uses it, and a host template's kernels where that host template is first used.  The map launchers
+// have always stood behind run_split and ahead of lslam_landmarks and lslam_ukf_step, whose
+// run_scan_kernel<MODE> bring the last scan_kernel instantiations; included behind this file instead,
+// the map side's kernel templates would land behind those.  Only fieldfuse_kernel belongs behind them,
+// as the code object's last: lslam_launch_map.h names the two run_scan_kernel<MODE> ahead of
+// launch_fieldfuse.  A new kernel goes behind every other first use, so that no kernel moves against
+// another.
+#include "lslam_launch_map.h"
 
 // ---- express-scan codec (lslam_express.h) ----
 
@@ -1595,288 +918,6 @@ int lslam_scan_pipeline(lslam_ctx *c, const lslam_scan_batch *b, const lslam_ran
     if (u && ((u->flags & LSLAM_UKF_SIGMAS_IN) || b->ukf_sigmas))
         return set_err(LSLAM_ERR_UNSUPPORTED, "ukf_sigmas / LSLAM_UKF_SIGMAS_IN are lslam_ukf_step's (filterpy's cache)");
     return run_split(c, b, p, u);
-}
-
-// (the checks that need no device come first, the context last: tests/test_scanmatch_ref.py)
-int lslam_scan_match(lslam_ctx *c, const lslam_match_batch *b, const lslam_match_params *p,
-                     const lslam_ukf_params *u) {
-    int st = match_check_params(p);
-    if (st) return st;
-    if (!b) return set_err(LSLAM_ERR_ARG, "match: batch is NULL");
-    if (b->n_scans < 0) return set_err(LSLAM_ERR_ARG, "match: negative n_scans");
-    if (b->n_scans > 0) {
-        if (!b->ref_xy || !b->ref_off || !b->cur_xy || !b->cur_off || !b->rot)
-            return set_err(LSLAM_ERR_ARG, "match: missing input (ref_xy, ref_off, cur_xy, cur_off, rot)");
-        if (!b->delta || !b->best || !b->n_valid || !b->flags)
-            return set_err(LSLAM_ERR_ARG, "match: missing output (delta, best, n_valid, flags)");
-        if (u && b->ukf_u && (!(u->dt > 0) || !(u->wheel_radius > 0)))
-            return set_err(LSLAM_ERR_ARG, "match: wheel speeds need dt > 0 and wheel_radius > 0");
-    }
-    if (!c) return set_err(LSLAM_ERR_ARG, "match: ctx is NULL");
-    if (b->n_scans == 0) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return launch_match(c, b, p, u);
-}
-
-// On the main stream: every pipeline call ends there (its post pass and lane-group UKF run on it,
-// and it waits for ev_ukf when the UKF ran on the side stream), so a ukf_x given as pose is final.
-int lslam_grid_update(lslam_ctx *c, const lslam_grid_batch *b, const lslam_grid_params *p) {
-    int st = grid_check_params(p);
-    if (st) return st;
-    if (!b) return set_err(LSLAM_ERR_ARG, "grid: batch is NULL");
-    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "grid: negative n_robots");
-    if (b->n_robots > 0) {
-        if (!b->xy || !b->pt_off || !b->pose || !b->origin)
-            return set_err(LSLAM_ERR_ARG, "grid: missing input (xy, pt_off, pose, origin)");
-        if (!b->logodds || !b->rot || !b->n_used || !b->flags)
-            return set_err(LSLAM_ERR_ARG, "grid: missing output (logodds, rot, n_used, flags)");
-    }
-    if (!c) return set_err(LSLAM_ERR_ARG, "grid: ctx is NULL");
-    if (b->n_robots == 0) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return launch_grid(c, b, p);
-}
-
-// On the main stream, as lslam_grid_update: a ukf_x given as pose is final, and so is the grid that
-// a preceding lslam_grid_update wrote.
-int lslam_map_match(lslam_ctx *c, const lslam_mapmatch_batch *b, const lslam_grid_params *g,
-                    const lslam_mapmatch_params *m) {
-    int st = mapmatch_check_params(m);
-    if (st) return st;
-    if ((st = grid_check_params(g))) return st;
-    if (!b) return set_err(LSLAM_ERR_ARG, "mapmatch: batch is NULL");
-    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "mapmatch: negative n_robots");
-    if (b->n_robots > 0) {
-        const int miss = mapmatch_missing(b);
-        if (miss == 1) return set_err(LSLAM_ERR_ARG, "mapmatch: missing input (xy, pt_off, pose, origin, logodds, rot)");
-        if (miss == 2)
-            return set_err(LSLAM_ERR_ARG, "mapmatch: missing output (pose_out, delta, best, n_valid, rot0, flags)");
-    }
-    if (!c) return set_err(LSLAM_ERR_ARG, "mapmatch: ctx is NULL");
-    if (b->n_robots == 0) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return launch_mapmatch(c, b, g, m);
-}
-
-// On the main stream, as lslam_map_match.
-int lslam_map_fuse(lslam_ctx *c, const lslam_mapfuse_batch *b, const lslam_grid_params *g,
-                   const lslam_mapmatch_params *m, const lslam_mapfuse_params *f) {
-    int st = mapmatch_check_params(m);
-    if (st) return st;
-    if ((st = grid_check_params(g))) return st;
-    if ((st = mapfuse_check_params(f))) return st;
-    if (!b) return set_err(LSLAM_ERR_ARG, "mapfuse: batch is NULL");
-    if (b->m.n_robots < 0) return set_err(LSLAM_ERR_ARG, "mapfuse: negative n_robots");
-    if (b->m.n_robots > 0) {
-        const int miss = mapmatch_missing(&b->m);
-        if (miss == 1 || !b->P)
-            return set_err(LSLAM_ERR_ARG, "mapfuse: missing input (xy, pt_off, pose, origin, logodds, rot, P)");
-        if (miss == 2 || !b->P_out || !b->z || !b->Rm || !b->nis)
-            return set_err(LSLAM_ERR_ARG,
-                           "mapfuse: missing output (pose_out, delta, best, n_valid, rot0, flags, P_out, z, Rm, nis)");
-    }
-    if (!c) return set_err(LSLAM_ERR_ARG, "mapfuse: ctx is NULL");
-    if (b->m.n_robots == 0) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return launch_mapfuse(c, b, g, m, f);
-}
-
-// On the main stream, as lslam_map_match.
-int lslam_map_relocalize(lslam_ctx *c, const lslam_reloc_batch *b, const lslam_grid_params *g,
-                         const lslam_mapmatch_params *m, const lslam_reloc_params *q) {
-    int st = mapmatch_check_params(m);
-    if (st) return st;
-    if ((st = grid_check_params(g))) return st;
-    if ((st = reloc_check_params(q, g, m))) return st;
-    if (!b) return set_err(LSLAM_ERR_ARG, "reloc: batch is NULL");
-    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "reloc: negative n_robots");
-    if (b->n_robots > 0) {
-        if (!b->xy || !b->pt_off || !b->origin || !b->logodds || !b->rot || !b->head_rot)
-            return set_err(LSLAM_ERR_ARG, "reloc: missing input (xy, pt_off, origin, logodds, rot, head_rot)");
-        if (!b->n_occ || !b->n_used || !b->cand || !b->cand_pose || !b->fine_pose || !b->fine_delta || !b->fine_best ||
-            !b->fine_nvalid || !b->fine_rot0 || !b->fine_flags || !b->result || !b->flags || !b->pose_out)
-            return set_err(LSLAM_ERR_ARG,
-                           "reloc: missing output (n_occ, n_used, cand, cand_pose, fine_pose, fine_delta, fine_best, "
-                           "fine_nvalid, fine_rot0, fine_flags, result, flags, pose_out)");
-    }
-    if (!c) return set_err(LSLAM_ERR_ARG, "reloc: ctx is NULL");
-    if (b->n_robots == 0) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return launch_reloc(c, b, g, m, q);
-}
-
-// On the main stream, as lslam_map_match.
-int lslam_grid_raycast(lslam_ctx *c, const lslam_raycast_batch *b, const lslam_grid_params *g,
-                       const lslam_raycast_params *p) {
-    int st = raycast_check_params(p);
-    if (st) return st;
-    if ((st = grid_check_params(g))) return st;
-    if (!b) return set_err(LSLAM_ERR_ARG, "raycast: batch is NULL");
-    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "raycast: negative n_robots");
-    if (b->n_robots > 0) {
-        if (!b->xy || !b->pt_off || !b->pose || !b->origin || !b->logodds)
-            return set_err(LSLAM_ERR_ARG, "raycast: missing input (xy, pt_off, pose, origin, logodds)");
-        if (!b->cls || !b->counts || !b->rot || !b->flags)
-            return set_err(LSLAM_ERR_ARG, "raycast: missing output (cls, counts, rot, flags)");
-    }
-    if (!c) return set_err(LSLAM_ERR_ARG, "raycast: ctx is NULL");
-    if (b->n_robots == 0) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return launch_raycast(c, b, g, p);
-}
-
-// On the main stream, as lslam_grid_update: ordered after the calls that read the grid where it was and
-// before the calls that read it where it is.
-int lslam_grid_recentre(lslam_ctx *c, const lslam_recentre_batch *b, const lslam_grid_params *g,
-                        const lslam_recentre_params *p) {
-    int st = grid_check_params(g);
-    if (st) return st;
-    if ((st = recentre_check_params(p, g))) return st;
-    if (!b) return set_err(LSLAM_ERR_ARG, "recentre: batch is NULL");
-    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "recentre: negative n_robots");
-    if (b->n_robots > 0) {
-        if (!b->pose || !b->origin || !b->logodds)
-            return set_err(LSLAM_ERR_ARG, "recentre: missing input (pose, origin, logodds)");
-        if (!b->shift || !b->flags) return set_err(LSLAM_ERR_ARG, "recentre: missing output (shift, flags)");
-    }
-    if (!c) return set_err(LSLAM_ERR_ARG, "recentre: ctx is NULL");
-    if (b->n_robots == 0) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return launch_recentre(c, b, g, p);
-}
-
-// On the main stream, as lslam_grid_raycast: after the calls that wrote the grid.
-int lslam_grid_distance(lslam_ctx *c, const lslam_dist_batch *b, const lslam_grid_params *g, const lslam_dist_params *p) {
-    int st = grid_check_params(g);
-    if (st) return st;
-    if ((st = dist_check_params(p))) return st;
-    if (!b) return set_err(LSLAM_ERR_ARG, "dist: batch is NULL");
-    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "dist: negative n_robots");
-    if (b->n_robots > 0) {
-        if (!b->logodds) return set_err(LSLAM_ERR_ARG, "dist: missing input (logodds)");
-        if (!b->d2 || !b->n_src || !b->flags) return set_err(LSLAM_ERR_ARG, "dist: missing output (d2, n_src, flags)");
-        const uintptr_t bytes = (uintptr_t)b->n_robots * (uintptr_t)g->grid_w * (uintptr_t)g->grid_w * 2;
-        const uintptr_t l0 = (uintptr_t)b->logodds, d0 = (uintptr_t)b->d2;
-        if (l0 < d0 + bytes && d0 < l0 + bytes) return set_err(LSLAM_ERR_ARG, "dist: d2 overlaps logodds");
-    }
-    if (!c) return set_err(LSLAM_ERR_ARG, "dist: ctx is NULL");
-    if (b->n_robots == 0) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return launch_dist(c, b, g, p);
-}
-
-// On the main stream, as lslam_grid_raycast.
-int lslam_field_score(lslam_ctx *c, const lslam_fieldscore_batch *b, const lslam_grid_params *g,
-                      const lslam_fieldscore_params *p) {
-    int st = grid_check_params(g);
-    if (st) return st;
-    if ((st = fieldscore_check_params(p))) return st;
-    if (!b) return set_err(LSLAM_ERR_ARG, "fieldscore: batch is NULL");
-    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "fieldscore: negative n_robots");
-    if (b->n_robots > 0) {
-        if (!b->xy || !b->pt_off || !b->pose || !b->origin || !b->d2)
-            return set_err(LSLAM_ERR_ARG, "fieldscore: missing input (xy, pt_off, pose, origin, d2)");
-        if (!b->rot || !b->stats || !b->clear2 || !b->flags)
-            return set_err(LSLAM_ERR_ARG, "fieldscore: missing output (rot, stats, clear2, flags)");
-    }
-    if (!c) return set_err(LSLAM_ERR_ARG, "fieldscore: ctx is NULL");
-    if (b->n_robots == 0) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return launch_fieldscore(c, b, g, p);
-}
-
-// On the main stream, as lslam_field_score.
-int lslam_field_align(lslam_ctx *c, const lslam_fieldalign_batch *b, const lslam_grid_params *g,
-                      const lslam_fieldalign_params *p) {
-    int st = grid_check_params(g);
-    if (st) return st;
-    if ((st = fieldalign_check_params(p))) return st;
-    if (!b) return set_err(LSLAM_ERR_ARG, "fieldalign: batch is NULL");
-    if (b->n_robots < 0) return set_err(LSLAM_ERR_ARG, "fieldalign: negative n_robots");
-    if (b->n_robots > 0) {
-        if (!b->xy || !b->pt_off || !b->pose || !b->origin || !b->d2)
-            return set_err(LSLAM_ERR_ARG, "fieldalign: missing input (xy, pt_off, pose, origin, d2)");
-        if (!b->pose_out || !b->trace || !b->normal || !b->n_used || !b->iters || !b->flags)
-            return set_err(LSLAM_ERR_ARG, "fieldalign: missing output (pose_out, trace, normal, n_used, iters, flags)");
-    }
-    if (!c) return set_err(LSLAM_ERR_ARG, "fieldalign: ctx is NULL");
-    if (b->n_robots == 0) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return launch_fieldalign(c, b, g, p);
-}
-
-// launch_fieldalign with pose_out := z, then one thread per robot for steps 5-11.  It stands here, behind
-// every other launch of the file, for fieldfuse_kernel's place in the code object: a kernel template is
-// emitted where it is first launched, and from here it lands behind the last scan_kernel instantiation,
-// so that no existing kernel moves against another.
-static int launch_fieldfuse(lslam_ctx *c, const lslam_fieldfuse_batch *b, const lslam_grid_params *g,
-                            const lslam_fieldalign_params *p, const lslam_fieldfuse_params *f) {
-    lslam_fieldalign_batch a = b->a;
-    a.pose_out = b->z;
-    int st = launch_fieldalign(c, &a, g, p);
-    if (st) return st;
-    FieldFuseArgs k;
-    memset(&k, 0, sizeof(k));
-    k.n_robots = b->a.n_robots;
-    k.pose = b->a.pose;
-    k.P = b->P;
-    k.z = b->z;
-    k.normal = b->a.normal;
-    k.n_used = b->a.n_used;
-    k.flags = b->a.flags;
-    k.pose_out = b->a.pose_out;
-    k.P_out = b->P_out;
-    k.info = b->info;
-    k.info_f = b->info_f;
-    k.s2 = b->s2;
-    k.nis = b->nis;
-    k.k = fieldfuse_consts(g->cell, f->sigma_min, f->r_scale, f->floor_t, f->floor_r, f->nis_max);
-    const size_t n = (size_t)b->a.n_robots;
-    const unsigned blocks = (unsigned)((n + FIELDFUSE_TPB - 1) / FIELDFUSE_TPB);
-    hipLaunchKernelGGL(fieldfuse_kernel<0>, dim3(blocks), dim3(FIELDFUSE_TPB), 0, c->stream, k);
-    HIPCHK(hipGetLastError());
-    c->hz.outs.add(b->a.pose_out, n * 24);
-    c->hz.outs.add(b->P_out, n * 72);
-    c->hz.outs.add(b->info, n * 72);
-    c->hz.outs.add(b->info_f, n * 72);
-    c->hz.outs.add(b->s2, n * 8);
-    c->hz.outs.add(b->nis, n * 8);
-    return LSLAM_OK;
-}
-
-// On the main stream, as lslam_field_align.
-int lslam_field_fuse(lslam_ctx *c, const lslam_fieldfuse_batch *b, const lslam_grid_params *g,
-                     const lslam_fieldalign_params *p, const lslam_fieldfuse_params *f) {
-    int st = grid_check_params(g);
-    if (st) return st;
-    if ((st = fieldalign_check_params(p))) return st;
-    if ((st = fieldfuse_check_params(f))) return st;
-    if (!b) return set_err(LSLAM_ERR_ARG, "fieldfuse: batch is NULL");
-    if (b->a.n_robots < 0) return set_err(LSLAM_ERR_ARG, "fieldfuse: negative n_robots");
-    if (b->a.n_robots > 0) {
-        const lslam_fieldalign_batch &a = b->a;
-        if (!a.xy || !a.pt_off || !a.pose || !a.origin || !a.d2 || !b->P)
-            return set_err(LSLAM_ERR_ARG, "fieldfuse: missing input (xy, pt_off, pose, origin, d2, P)");
-        if (!a.pose_out || !a.trace || !a.normal || !a.n_used || !a.iters || !a.flags || !b->P_out || !b->z || !b->info ||
-            !b->info_f || !b->s2 || !b->nis)
-            return set_err(LSLAM_ERR_ARG, "fieldfuse: missing output (pose_out, trace, normal, n_used, iters, flags, P_out, "
-                                          "z, info, info_f, s2, nis)");
-        const size_t n = (size_t)a.n_robots;
-        if (fieldfuse_overlap(b->z, n * 24, a.pose, n * 24) || fieldfuse_overlap(b->z, n * 24, a.pose_out, n * 24) ||
-            fieldfuse_overlap(b->z, n * 24, b->P, n * 72) || fieldfuse_overlap(b->z, n * 24, b->P_out, n * 72))
-            return set_err(LSLAM_ERR_ARG, "fieldfuse: z must not overlap pose, pose_out, P or P_out");
-    }
-    if (!c) return set_err(LSLAM_ERR_ARG, "fieldfuse: ctx is NULL");
-    if (b->a.n_robots == 0) return LSLAM_OK;
-    HIPCHK(hipSetDevice(c->device));
-    return launch_fieldfuse(c, b, g, p, f);
-}
-
-// (the scratch is sized per call: a call in flight keeps the chunking it was launched with)
-int lslam_set_reloc_budget(lslam_ctx *c, int64_t bytes) {
-    if (!c) return LSLAM_ERR_ARG;
-    c->reloc_budget = bytes > 0 ? (size_t)bytes : default_reloc_budget();
-    return LSLAM_OK;
 }
 
 int lslam_express_decode(lslam_ctx *c, const uint8_t *packets, int64_t n_packets, const lslam_express_measures *out) {
