@@ -171,7 +171,8 @@ class LidarOdometry:
         of ``xy`` (host array, ``DeviceArray`` or a ``MapInput``).  The first call stores the
         revolution and writes u = 0; later calls match previous -> current and, given a
         ``LandmarkMap`` ``lm``, write the wheel speeds into ``lm.u`` on the device (with lm's dt,
-        wheel radius and wheel base), where ``lm.step(...)`` without ``u`` finds them."""
+        wheel radius and wheel base), where ``lm.step(...)`` without ``u`` finds them.  Given device
+        points and ``sync=False`` a step waits for the host only where a longer revolution grows a copy."""
         ctx, R = self.ctx, self.R
         if isinstance(xy, MapInput):
             xy, scan_chunk_off, chunk_pt_off = xy.xy, xy.sco, xy.cpo
@@ -186,6 +187,8 @@ class LidarOdometry:
             raise ValueError("inconsistent CSR offsets")
         # the caller's device array may be an express ring that the next step overwrites: copy
         cur = self._xy[1].reserve(2 * n)
+        if self.steps == 0:
+            self._xy[0].reserve(2 * n)  # both copies are sized by the first step: the second one's grow would sync
         if isinstance(xy, DeviceArray):
             if xy.dtype != np.float64 or xy.nbytes < 16 * p1:
                 raise ValueError("device xy must be float64 [n, 2] with n >= the last point offset")
@@ -196,7 +199,8 @@ class LidarOdometry:
             if h.shape[0] < p1:
                 raise ValueError("xy holds fewer points than chunk_pt_off describes")
             self._xy[1].put_host(h[p0:p1])
-        self._off[1].upload((off - p0).astype(np.int32))
+        # on the stream, behind the match that read this buffer two steps ago (ctx._inflight holds the array)
+        self._off[1].upload_async(np.ascontiguousarray(off - p0, np.int32))
         self._n[1] = n
         if self.steps == 0:
             if lm is not None:
