@@ -429,6 +429,25 @@ typedef struct lslam_reloc_batch {
     int32_t *coarse_scores;   /* [n_robots][n_head][Wc][Wc] the whole coarse volume (optional) */
 } lslam_reloc_batch;
 
+/* Relocalisation priors (lslam_map_relocalize_prior), 24 bytes. */
+typedef struct lslam_relocprior_params {
+    double half_xy;      /* mm, >= 0, +inf: no box; half side of the window box around win_pose (x, y) (1000.0) */
+    double half_theta;   /* rad, >= 0, +inf: every heading (0.5) */
+    int32_t clear_min2;  /* squared fine cells, 0..65025 (16: four cells, one default coarse cell) */
+    int32_t reserved;
+} lslam_relocprior_params;
+
+/* lslam_reloc_batch with the priors and their two outputs, 208 bytes; all pointers DEVICE memory,
+ * clear_d2 and win_pose optional, n_admit and fine_clear2 required. */
+typedef struct lslam_relocprior_batch {
+    lslam_reloc_batch r;       /* as it is, every rule of lslam_map_relocalize */
+    const uint16_t *clear_d2;  /* [n_robots][grid_w][grid_w] the NOT_FREE field of lslam_grid_distance (optional) */
+    const double *win_pose;    /* [n_robots][3] the centre of the search window, e.g. the stale ukf_x (optional) */
+    int32_t *n_admit;          /* [n_robots][2] admissible coarse cells, admissible headings */
+    int32_t *fine_clear2;      /* [K][n_robots] d2 at the refined pose's cell; -1 off the map or rank missing;
+                                  0 if clear_d2 is NULL */
+} lslam_relocprior_batch;
+
 /* ---- grid ray-cast flags (lslam_raycast_batch.flags), beam classes and stop kinds (cls) ---- */
 enum {
     LSLAM_RAYCAST_BAD_POSE = 1  /* as LSLAM_GRID_BAD_POSE: nothing is cast */
@@ -694,6 +713,8 @@ int lslam_dist_abi_sizes(int64_t *sizes, int n);
 int lslam_fieldalign_abi_sizes(int64_t *sizes, int n);
 /* and for lslam_fieldfuse_params, lslam_fieldfuse_batch.  Writes min(n, 2) entries, returns 2. */
 int lslam_fieldfuse_abi_sizes(int64_t *sizes, int n);
+/* and for lslam_relocprior_params, lslam_relocprior_batch.  Writes min(n, 2) entries, returns 2. */
+int lslam_relocprior_abi_sizes(int64_t *sizes, int n);
 /* per-kernel HIP-event timing on the ctx stream (kernel ids: LSLAM_K_*) */
 enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMARK = 3, LSLAM_K_UKF = 4,
        LSLAM_K_RNG = 5 /* parity-stream producer */, LSLAM_K_CONSENSUS = 6 /* per-chunk A4-A8 */,
@@ -735,6 +756,7 @@ int lslam_dist_params_default(lslam_dist_params *p);
 int lslam_fieldscore_params_default(lslam_fieldscore_params *p);
 int lslam_fieldalign_params_default(lslam_fieldalign_params *p);
 int lslam_fieldfuse_params_default(lslam_fieldfuse_params *p);
+int lslam_relocprior_params_default(lslam_relocprior_params *p);
 /* smallest e with RN(sqrt(e)) >= thr: (residual < thr) <=> (squared residual < cutoff) */
 double lslam_inlier_cutoff(double thr);
 /* MerweScaledSigmaPoints weights (filterpy _compute_weights) for n = 3 */
@@ -1221,6 +1243,42 @@ int lslam_field_align(lslam_ctx *ctx, const lslam_fieldalign_batch *b, const lsl
  * does nothing. */
 int lslam_field_fuse(lslam_ctx *ctx, const lslam_fieldfuse_batch *b, const lslam_grid_params *g,
                      const lslam_fieldalign_params *p, const lslam_fieldfuse_params *f);
+
+/* Relocalisation with priors: lslam_map_relocalize over a set of admissible coarse candidates, the cells
+ * where the clearance field says a robot can stand and the cells and headings of a window around a stale
+ * pose.  A candidate outside the set scores 0 and is not searched.  b->r, g, m and q are checked as
+ * lslam_map_relocalize checks them, pp as its table says.  Per robot r it is steps 0-6 of
+ * lslam_map_relocalize, verbatim, with b->r, but for the following; f, Wc, cellc as there, (ox, oy) the
+ * robot's origin, (wx, wy, wtheta) = win_pose[r]:
+ *   field admissibility: Af[ty][tx] = 1 iff some fine cell of the f x f block of coarse cell (ty, tx) has
+ *      clear_d2 >= clear_min2; all ones if clear_d2 is NULL.  The rule is lenient on purpose: the fine
+ *      stage moves the pose inside the block, and step 5' is the strict test.
+ *   window admissibility: cx = ox + ((double)tx + 0.5) cellc, cy = oy + ((double)ty + 0.5) cellc
+ *      (cand_pose's own expressions).  Aw[ty][tx] = 1 iff fabs(cx - wx) <= half_xy and
+ *      fabs(cy - wy) <= half_xy.  H[k] = 1 iff fabs(remainder((double)k head_step - wtheta,
+ *      6.283185307179586)) <= half_theta, remainder being the IEEE operation (exact).  With win_pose NULL,
+ *      Aw and H are all ones.  A NaN in win_pose makes its comparisons false: nothing is admissible, and
+ *      the robot ends LOST by the rules below, with no special case.
+ *   counts: n_admit[r] = (the number of cells with Af & Aw, the number of k with H).
+ *   2'. Sc'[k][ty][tx] = Sc[k][ty][tx] where Af & Aw & H[k], else 0.  Step 3 runs on Sc' unchanged: a peak
+ *      needs a score > 0 and a 0 never comes before a positive candidate, so an inadmissible cell is
+ *      never a candidate and never suppresses one.  coarse_scores, if given, receives Sc'.
+ *   5'. fine_clear2[j][r]: with (X0, Y0) the cell of fine_pose[j] by step 0 of lslam_grid_update (as
+ *      lslam_field_score takes clear2), clear_d2[Y0][X0]; -1 where that step calls the pose bad (a missing
+ *      rank's NaNs are) or the cell is off the map; 0 everywhere if clear_d2 is NULL.  Rank j is eligible
+ *      iff step 5's rule holds and, when clear_d2 is given, fine_clear2[j][r] >= clear_min2.
+ * Preconditions the call cannot check: clear_d2 is the LSLAM_DIST_NOT_FREE field of the same logodds,
+ * computed with d_max d_max >= clear_min2.  clear_d2 must overlap no output (LSLAM_ERR_ARG).
+ * Identity: with clear_d2 and win_pose both NULL every output of b->r equals lslam_map_relocalize's bit
+ * for bit.  No result depends on the chunking of lslam_set_reloc_budget.  The admissible set is built
+ * once per robot (a bit per coarse cell, a list of headings); the search then runs only over the spans
+ * of 32 cells that hold an admissible one and over the admissible headings (lslam_relocprior.h).  Runs on
+ * the context's main stream, under LSLAM_K_RELOC.  Out-of-range parameters and missing pointers return
+ * LSLAM_ERR_ARG (the message names the field), checked before the context is touched; n_robots == 0
+ * does nothing. */
+int lslam_map_relocalize_prior(lslam_ctx *ctx, const lslam_relocprior_batch *b, const lslam_grid_params *g,
+                               const lslam_mapmatch_params *m, const lslam_reloc_params *q,
+                               const lslam_relocprior_params *pp);
 
 #ifdef __cplusplus
 }

@@ -150,6 +150,14 @@ class RelocBatch(C.Structure):
                                    "fine_flags", "result", "flags", "pose_out", "P_out", "coarse_scores")]
 
 
+class RelocPriorParams(C.Structure):
+    _fields_ = [("half_xy", C.c_double), ("half_theta", C.c_double), ("clear_min2", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RelocPriorBatch(C.Structure):
+    _fields_ = [("r", RelocBatch)] + [(n, _VP) for n in ("clear_d2", "win_pose", "n_admit", "fine_clear2")]
+
+
 class RaycastParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("occ_min", "free_max", "tol", "reserved")]
 
@@ -228,6 +236,7 @@ EXPORTS = [
     "lslam_grid_distance", "lslam_field_score",
     "lslam_fieldalign_abi_sizes", "lslam_fieldalign_params_default", "lslam_field_align",
     "lslam_fieldfuse_abi_sizes", "lslam_fieldfuse_params_default", "lslam_field_fuse",
+    "lslam_relocprior_abi_sizes", "lslam_relocprior_params_default", "lslam_map_relocalize_prior",
 ]
 
 _lib = None
@@ -323,6 +332,10 @@ def load():
         "lslam_fieldfuse_abi_sizes": ([P(i64), C.c_int], C.c_int),
         "lslam_fieldfuse_params_default": ([P(FieldFuseParams)], C.c_int),
         "lslam_field_fuse": ([_VP, P(FieldFuseBatch), P(GridParams), P(FieldAlignParams), P(FieldFuseParams)], C.c_int),
+        "lslam_relocprior_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_relocprior_params_default": ([P(RelocPriorParams)], C.c_int),
+        "lslam_map_relocalize_prior": ([_VP, P(RelocPriorBatch), P(GridParams), P(MapMatchParams), P(RelocParams),
+                                        P(RelocPriorParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -373,6 +386,7 @@ _ABI_SIZES = [
     ("lslam_dist_abi_sizes", (DistParams, DistBatch, FieldScoreParams, FieldScoreBatch)),
     ("lslam_fieldalign_abi_sizes", (FieldAlignParams, FieldAlignBatch)),
     ("lslam_fieldfuse_abi_sizes", (FieldFuseParams, FieldFuseBatch)),
+    ("lslam_relocprior_abi_sizes", (RelocPriorParams, RelocPriorBatch)),
 ]
 
 
@@ -427,6 +441,7 @@ dist_params = _params_factory("dist", DistParams)
 fieldscore_params = _params_factory("fieldscore", FieldScoreParams)
 fieldalign_params = _params_factory("fieldalign", FieldAlignParams)
 fieldfuse_params = _params_factory("fieldfuse", FieldFuseParams)
+relocprior_params = _params_factory("relocprior", RelocPriorParams)
 
 
 def ukf_params(n_landmarks, **kw):

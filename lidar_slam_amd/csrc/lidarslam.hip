@@ -15,7 +15,8 @@
 //   field of the grid and its reader; the two 1-D passes are lslam_dist_core.h, plain C++),
 //   lslam_fieldalign.h (the Gauss-Newton alignment in the field; a point's terms and the 3 x 3 solve
 //   are lslam_fieldalign_core.h, plain C++), lslam_fieldfuse.h (the alignment fused into the filter; its
-//   3 x 3 algebra is lslam_fieldfuse_core.h, plain C++);
+//   3 x 3 algebra is lslam_fieldfuse_core.h, plain C++), lslam_relocprior.h (relocalisation over an
+//   admissible set: the free-space prior and the search window);
 // the host side is included at the foot:
 //   lslam_hazards.h  which waits a call's producer needs (plain C++, no HIP)
 //   lslam_ctx.h      lslam_ctx, its grow-only device buffers and timers, create / destroy,
@@ -3077,6 +3078,8 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
 // the field fusion's kernel, a template: emitted behind every other (lslam_launch.h, at its include of
 // lslam_launch_map.h)
 #include "lslam_fieldfuse.h"
+// the relocalisation priors' three kernels, templates too: the newest, so the code object's last
+#include "lslam_relocprior.h"
 
 // ------------------------------------------------------------------------
 // host side: the context, then the launchers and entry points

@@ -428,6 +428,12 @@ int lslam_fieldfuse_abi_sizes(int64_t *sizes, int n) {
     return 2;
 }
 
+int lslam_relocprior_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[2] = {(int64_t)sizeof(lslam_relocprior_params), (int64_t)sizeof(lslam_relocprior_batch)};
+    for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
+    return 2;
+}
+
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
     if (!c || (!dst && n)) return LSLAM_ERR_ARG;
     if (!n) return LSLAM_OK;
@@ -657,6 +663,15 @@ int lslam_fieldfuse_params_default(lslam_fieldfuse_params *p) {
     p->floor_t = 1.0 / sqrt(12.0);                  // cells: one cell's quantum, as lslam_map_fuse's search quantum
     p->floor_r = (LS_PI / 360.0) / sqrt(12.0);      // rad: the matcher's heading quantum, so the two measurements floor alike
     p->nis_max = 16.27;                             // the 99.9 % point of chi-square with 3 degrees of freedom
+    return LSLAM_OK;
+}
+
+int lslam_relocprior_params_default(lslam_relocprior_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->half_xy = 1000.0;   // mm: a filter that has drifted a metre ...
+    p->half_theta = 0.5;   // ... and twenty-odd degrees still has its pose inside the window
+    p->clear_min2 = 16;    // four fine cells: one coarse cell at the default factor
     return LSLAM_OK;
 }
 

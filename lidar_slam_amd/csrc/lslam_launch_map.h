@@ -424,14 +424,10 @@ static int launch_reloc_search(lslam_ctx *c, const RelocArgs &k, int nr) {
     return LSLAM_OK;
 }
 
-// The coarse stage in chunks of robots under the context's byte budget (search, peaks, the K best),
-// then K times the scan-to-map matcher (launch_mapmatch_kernels), rank j's arrays in the place of
-// the batch's, then the selection.  LSLAM_RELOC_FORM=add (tools/relocbench.py) selects the search
-// form that was measured and dropped.
-static int launch_reloc(lslam_ctx *c, const lslam_reloc_batch *b, const lslam_grid_params *g,
-                        const lslam_mapmatch_params *m, const lslam_reloc_params *q) {
-    const int R = b->n_robots, K = q->n_cand;
-    RelocArgs k;
+// The kernels' arguments of a relocalisation but for the chunk's (r0, vol, keys) and the slicing; returns
+// the cells of one robot's coarse volume.
+static size_t reloc_args(const lslam_reloc_batch *b, const lslam_grid_params *g, const lslam_mapmatch_params *m,
+                         const lslam_reloc_params *q, RelocArgs &k) {
     memset(&k, 0, sizeof(k));
     k.b = *b;
     k.f = q->factor;
@@ -446,17 +442,74 @@ static int launch_reloc(lslam_ctx *c, const lslam_reloc_batch *b, const lslam_gr
     k.pth = q->reset_sigma_theta * q->reset_sigma_theta;
     k.map_w = g->grid_w;
     k.n_head = q->n_head;
-    k.K = K;
+    k.K = q->n_cand;
     k.occ_min = m->occ_min;
     k.ambig = q->ambig_permille;
     k.nspan = (k.Wc + 31) / 32;
     k.RW = reloc_row_dwords(k.Wc, k.nspan);
     k.vec = groups16(g->grid_w, b->logodds);
-    if (const char *e = getenv("LSLAM_RELOC_FORM"))
-        if (!strcmp(e, "add")) k.form = 1;
-    const size_t cells = (size_t)k.n_head * k.Wc * k.Wc;
     k.nbh = (k.Wc * k.Wc + RELOC_PEAK_BLOCK - 1) / RELOC_PEAK_BLOCK;
     k.nblk = k.n_head * k.nbh;
+    return (size_t)k.n_head * k.Wc * k.Wc;
+}
+
+// the fine stage's batch but for the rank's arrays
+static void reloc_fine_batch(const lslam_reloc_batch *b, lslam_mapmatch_batch &mb) {
+    memset(&mb, 0, sizeof(mb));
+    mb.n_robots = b->n_robots;
+    mb.xy = b->xy;
+    mb.pt_off = b->pt_off;
+    mb.origin = b->origin;
+    mb.logodds = b->logodds;
+    mb.rot = b->rot;
+}
+
+// K times the scan-to-map matcher (launch_mapmatch_kernels), rank j's arrays in the place of the batch's
+static int launch_reloc_fine(lslam_ctx *c, const lslam_reloc_batch *b, const lslam_grid_params *g,
+                             const lslam_mapmatch_params *m, int K, lslam_mapmatch_batch &mb) {
+    const size_t Rz = (size_t)b->n_robots;
+    MapMatchArgs mk;
+    size_t mvol;
+    for (int j = 0; j < K; j++) {
+        mb.pose = b->cand_pose + (size_t)j * Rz * 3;
+        mb.pose_out = b->fine_pose + (size_t)j * Rz * 3;
+        mb.delta = b->fine_delta + (size_t)j * Rz * 3;
+        mb.best = b->fine_best + (size_t)j * Rz * 4;
+        mb.n_valid = b->fine_nvalid + (size_t)j * Rz * 2;
+        mb.rot0 = b->fine_rot0 + (size_t)j * Rz * 2;
+        mb.flags = b->fine_flags + (size_t)j * Rz;
+        int st = mapmatch_args(c, &mb, g, m, mk, mvol);  // (the stream orders the reuse of its scratch)
+        if (st || (st = launch_mapmatch_kernels(c, mk))) return st;
+    }
+    return LSLAM_OK;
+}
+
+// a relocalisation's outputs, for the hazard planner
+static int reloc_outs(lslam_ctx *c, const lslam_reloc_batch *b, int K, size_t cells) {
+    const size_t Rz = (size_t)b->n_robots, KR = (size_t)K * Rz;
+    return note_outs(c, {{b->n_occ, Rz * 4}, {b->n_used, Rz * 4}, {b->cand, KR * 16}, {b->cand_pose, KR * 24},
+                         {b->fine_pose, KR * 24}, {b->fine_delta, KR * 24}, {b->fine_best, KR * 16}, {b->fine_nvalid, KR * 8},
+                         {b->fine_rot0, KR * 16}, {b->fine_flags, KR * 4}, {b->result, Rz * 32}, {b->flags, Rz * 4},
+                         {b->pose_out, Rz * 24}, {b->P_out, Rz * 72}, {b->coarse_scores, Rz * cells * 4}});
+}
+
+// LSLAM_RELOC_STAGES=coarse (tools/relocbench.py): the coarse stage alone; the fine outputs, result, flags
+// and pose_out are not written
+static bool reloc_coarse_only() {
+    const char *stages = getenv("LSLAM_RELOC_STAGES");
+    return stages && !strcmp(stages, "coarse");
+}
+
+// The coarse stage in chunks of robots under the context's byte budget (search, peaks, the K best),
+// then the fine stage, then the selection.  LSLAM_RELOC_FORM=add (tools/relocbench.py) selects the search
+// form that was measured and dropped.
+static int launch_reloc(lslam_ctx *c, const lslam_reloc_batch *b, const lslam_grid_params *g,
+                        const lslam_mapmatch_params *m, const lslam_reloc_params *q) {
+    const int R = b->n_robots, K = q->n_cand;
+    RelocArgs k;
+    const size_t cells = reloc_args(b, g, m, q, k);
+    if (const char *e = getenv("LSLAM_RELOC_FORM"))
+        if (!strcmp(e, "add")) k.form = 1;
     const int nc = (int)std::min<size_t>((size_t)R, std::max<size_t>(1, c->reloc_budget / (cells * 4)));
     const int64_t ns = slices_for(c, nc, k.n_head);
     k.per_slice = (int)((k.n_head + ns - 1) / ns);
@@ -468,13 +521,7 @@ static int launch_reloc(lslam_ctx *c, const lslam_reloc_batch *b, const lslam_gr
     k.keys = c->rscr.as<unsigned long long>();
     // the fine stage's batch of rank 0: its scratch is grown here, before the timer and the first launch
     lslam_mapmatch_batch mb;
-    memset(&mb, 0, sizeof(mb));
-    mb.n_robots = R;
-    mb.xy = b->xy;
-    mb.pt_off = b->pt_off;
-    mb.origin = b->origin;
-    mb.logodds = b->logodds;
-    mb.rot = b->rot;
+    reloc_fine_batch(b, mb);
     MapMatchArgs mk;
     size_t mvol;
     if ((st = mapmatch_args(c, &mb, g, m, mk, mvol))) return st;
@@ -489,30 +536,12 @@ static int launch_reloc(lslam_ctx *c, const lslam_reloc_batch *b, const lslam_gr
         hipLaunchKernelGGL(reloc_topk_kernel, dim3((unsigned)nr), dim3(RELOC_PEAK_TPB), 0, c->stream, k);
         HIPCHK(hipGetLastError());
     }
-    const size_t Rz = (size_t)R;
-    // LSLAM_RELOC_STAGES=coarse (tools/relocbench.py): the coarse stage alone; the fine outputs, result, flags
-    // and pose_out are not written
-    const char *stages = getenv("LSLAM_RELOC_STAGES");
-    if (stages && !strcmp(stages, "coarse")) return timer_end(c, LSLAM_K_RELOC);
-    for (int j = 0; j < K; j++) {
-        mb.pose = b->cand_pose + (size_t)j * Rz * 3;
-        mb.pose_out = b->fine_pose + (size_t)j * Rz * 3;
-        mb.delta = b->fine_delta + (size_t)j * Rz * 3;
-        mb.best = b->fine_best + (size_t)j * Rz * 4;
-        mb.n_valid = b->fine_nvalid + (size_t)j * Rz * 2;
-        mb.rot0 = b->fine_rot0 + (size_t)j * Rz * 2;
-        mb.flags = b->fine_flags + (size_t)j * Rz;
-        if ((st = mapmatch_args(c, &mb, g, m, mk, mvol))) return st;  // (the stream orders the reuse of its scratch)
-        if ((st = launch_mapmatch_kernels(c, mk))) return st;
-    }
+    if (reloc_coarse_only()) return timer_end(c, LSLAM_K_RELOC);
+    if ((st = launch_reloc_fine(c, b, g, m, K, mb))) return st;
     hipLaunchKernelGGL(reloc_select_kernel, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, c->stream, k);
     HIPCHK(hipGetLastError());
     if ((st = timer_end(c, LSLAM_K_RELOC))) return st;
-    const size_t KR = (size_t)K * Rz;
-    return note_outs(c, {{b->n_occ, Rz * 4}, {b->n_used, Rz * 4}, {b->cand, KR * 16}, {b->cand_pose, KR * 24},
-                         {b->fine_pose, KR * 24}, {b->fine_delta, KR * 24}, {b->fine_best, KR * 16}, {b->fine_nvalid, KR * 8},
-                         {b->fine_rot0, KR * 16}, {b->fine_flags, KR * 4}, {b->result, Rz * 32}, {b->flags, Rz * 4},
-                         {b->pose_out, Rz * 24}, {b->P_out, Rz * 72}, {b->coarse_scores, Rz * cells * 4}});
+    return reloc_outs(c, b, K, cells);
 }
 
 // ---- grid ray casting (lslam_raycast.h) ----
@@ -827,6 +856,117 @@ static int launch_fieldfuse(lslam_ctx *c, const lslam_fieldfuse_batch *b, const 
                          {b->nis, n * 8}});
 }
 
+// ---- relocalisation priors (lslam_relocprior.h) ----
+// Behind launch_fieldfuse: its three kernel templates are the newest, so they take the code object's end
+// (lslam_launch.h, at this file's include).
+
+static int relocprior_check_params(const lslam_relocprior_params *pp) {
+    if (!pp) return set_err(LSLAM_ERR_ARG, "relocprior: params is NULL");
+    if (!(pp->half_xy >= 0)) return set_err(LSLAM_ERR_ARG, "relocprior: half_xy must be >= 0 (+inf: no box)");
+    if (!(pp->half_theta >= 0)) return set_err(LSLAM_ERR_ARG, "relocprior: half_theta must be >= 0 (+inf: every heading)");
+    if (pp->clear_min2 < 0 || pp->clear_min2 > 65025) return set_err(LSLAM_ERR_ARG, "relocprior: clear_min2 must be in [0, 65025]");
+    return LSLAM_OK;
+}
+
+static Reqs relocprior_reqs(const lslam_relocprior_batch &b) {
+    return reqs_join(reloc_reqs(b.r), {{}, {{"n_admit", b.n_admit}, {"fine_clear2", b.fine_clear2}}});
+}
+
+// clear_d2 overlaps no output
+static int relocprior_check_overlap(const lslam_relocprior_batch *b, const lslam_grid_params *g, const lslam_reloc_params *q) {
+    if (!b->clear_d2) return LSLAM_OK;
+    const lslam_reloc_batch &r = b->r;
+    const size_t Rz = (size_t)r.n_robots, KR = (size_t)q->n_cand * Rz, Wc = (size_t)(g->grid_w / q->factor);
+    const size_t bytes = Rz * (size_t)g->grid_w * (size_t)g->grid_w * 2;
+    const Out outs[] = {{r.n_occ, Rz * 4}, {r.n_used, Rz * 4}, {r.cand, KR * 16}, {r.cand_pose, KR * 24}, {r.fine_pose, KR * 24},
+                        {r.fine_delta, KR * 24}, {r.fine_best, KR * 16}, {r.fine_nvalid, KR * 8}, {r.fine_rot0, KR * 16},
+                        {r.fine_flags, KR * 4}, {r.result, Rz * 32}, {r.flags, Rz * 4}, {r.pose_out, Rz * 24}, {r.P_out, Rz * 72},
+                        {r.coarse_scores, Rz * (size_t)q->n_head * Wc * Wc * 4}, {b->n_admit, Rz * 8}, {b->fine_clear2, KR * 4}};
+    for (const Out &o : outs)
+        if (o.p && ranges_overlap(b->clear_d2, bytes, o.p, o.bytes)) return set_err(LSLAM_ERR_ARG, "relocprior: clear_d2 overlaps an output");
+    return LSLAM_OK;
+}
+
+// launch_reloc over the admissible set: the admissible bits and headings of every robot once, then per
+// chunk the volume cleared (the search leaves dead spans and skipped headings alone), the search over
+// the live spans, lslam_map_relocalize's own peak and top-K kernels, its fine stage, and the selection
+// with the clearance test.  With neither prior the set is everything: the plain search kernel runs, with
+// no clear, between the same admissibility pass (n_admit) and selection (fine_clear2).
+static int launch_relocprior(lslam_ctx *c, const lslam_relocprior_batch *pb, const lslam_grid_params *g,
+                             const lslam_mapmatch_params *m, const lslam_reloc_params *q, const lslam_relocprior_params *pp) {
+    const lslam_reloc_batch *b = &pb->r;
+    const int R = b->n_robots, K = q->n_cand;
+    RelocPriorArgs pa;
+    memset(&pa, 0, sizeof(pa));
+    RelocArgs &k = pa.r;
+    const size_t cells = reloc_args(b, g, m, q, k);
+    pa.clear_d2 = pb->clear_d2;
+    pa.win_pose = pb->win_pose;
+    pa.n_admit = pb->n_admit;
+    pa.fine_clear2 = pb->fine_clear2;
+    pa.half_xy = pp->half_xy;
+    pa.half_theta = pp->half_theta;
+    pa.inv = 1.0 / g->cell;
+    pa.clear_min2 = pp->clear_min2;
+    pa.vec_d = groups16(g->grid_w, pb->clear_d2);
+    const bool prior = pb->clear_d2 || pb->win_pose;
+    const int nc = (int)std::min<size_t>((size_t)R, std::max<size_t>(1, c->reloc_budget / (cells * 4)));
+    const int64_t ns = slices_for(c, nc, k.n_head);
+    if (prior) {
+        k.n_slices = (int)ns;  // of the robot's admissible headings: the kernel divides them
+    } else {  // every cell and heading is admissible: the plain search, sliced as launch_reloc slices it
+        k.per_slice = (int)((k.n_head + ns - 1) / ns);
+        k.n_slices = (k.n_head + k.per_slice - 1) / k.per_slice;
+    }
+    int st = check_blocks("relocprior", (int64_t)nc * k.nblk);
+    if (st) return st;
+    // the scratch: the chunk's keys, every robot's bits and headings, the chunk's volume
+    const size_t ntask = (size_t)k.Wc * k.nspan;
+    const size_t keys_bytes = ((size_t)nc * k.nblk * K * 8 + 255) & ~(size_t)255;
+    const size_t bits_bytes = ((size_t)R * ntask * 4 + 255) & ~(size_t)255;
+    const size_t heads_bytes = ((size_t)R * (k.n_head + 1) * 4 + 255) & ~(size_t)255;
+    const size_t vol_off = keys_bytes + bits_bytes + heads_bytes;
+    if ((st = c->rscr.ensure(c, vol_off + (b->coarse_scores ? 0 : (size_t)nc * cells * 4), "reloc scratch"))) return st;
+    k.keys = c->rscr.as<unsigned long long>();
+    pa.bits = (uint32_t *)(c->rscr.as<char>() + keys_bytes);
+    pa.heads = (int32_t *)(c->rscr.as<char>() + keys_bytes + bits_bytes);
+    lslam_mapmatch_batch mb;
+    reloc_fine_batch(b, mb);
+    MapMatchArgs mk;
+    size_t mvol;
+    if ((st = mapmatch_args(c, &mb, g, m, mk, mvol))) return st;
+    static std::once_flag once;
+    std::call_once(once, [] { set_max_lds(relocprior_search_kernel<0>); });
+    if ((st = timer_begin(c, LSLAM_K_RELOC))) return st;
+    hipLaunchKernelGGL(relocprior_admit_kernel<0>, dim3((unsigned)R), dim3(RELOCPRIOR_ADMIT_TPB), 0, c->stream, pa);
+    HIPCHK(hipGetLastError());
+    for (int r0 = 0; r0 < R; r0 += nc) {
+        const int nr = std::min(nc, R - r0);
+        k.r0 = r0;
+        k.vol = b->coarse_scores ? b->coarse_scores + (size_t)r0 * cells : (int32_t *)(c->rscr.as<char>() + vol_off);
+        if (prior) {
+            HIPCHK(hipMemsetAsync(k.vol, 0, (size_t)nr * cells * 4, c->stream));
+            hipLaunchKernelGGL(relocprior_search_kernel<0>, dim3((unsigned)(nr * k.n_slices)), dim3(RELOC_TPB),
+                               relocprior_lds_bytes(k.Wc, k.RW, k.nspan), c->stream, pa);
+            HIPCHK(hipGetLastError());
+        } else if ((st = launch_reloc_search<0>(c, k, nr))) {
+            return st;
+        }
+        hipLaunchKernelGGL(reloc_peak_kernel, dim3((unsigned)(nr * k.nblk)), dim3(RELOC_PEAK_TPB), 0, c->stream, k);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL(reloc_topk_kernel, dim3((unsigned)nr), dim3(RELOC_PEAK_TPB), 0, c->stream, k);
+        HIPCHK(hipGetLastError());
+    }
+    const size_t Rz = (size_t)R;
+    if (reloc_coarse_only()) return timer_end(c, LSLAM_K_RELOC);
+    if ((st = launch_reloc_fine(c, b, g, m, K, mb))) return st;
+    hipLaunchKernelGGL(relocprior_select_kernel<0>, dim3((unsigned)((R + 63) / 64)), dim3(64), 0, c->stream, pa);
+    HIPCHK(hipGetLastError());
+    if ((st = timer_end(c, LSLAM_K_RELOC))) return st;
+    if ((st = reloc_outs(c, b, K, cells))) return st;
+    return note_outs(c, {{pb->n_admit, Rz * 8}, {pb->fine_clear2, (size_t)K * Rz * 4}});
+}
+
 // ---- the entry points: the params checks (which of two wrong ones wins is their order), then the frame ----
 
 extern "C" {
@@ -940,6 +1080,17 @@ int lslam_field_fuse(lslam_ctx *c, const lslam_fieldfuse_batch *b, const lslam_g
             return LSLAM_OK;
         },
         [&] { return launch_fieldfuse(c, b, g, p, f); });
+}
+
+// On the main stream, as lslam_map_relocalize.
+int lslam_map_relocalize_prior(lslam_ctx *c, const lslam_relocprior_batch *b, const lslam_grid_params *g,
+                               const lslam_mapmatch_params *m, const lslam_reloc_params *q,
+                               const lslam_relocprior_params *pp) {
+    int st = mapmatch_check_params(m);
+    if (st || (st = grid_check_params(g)) || (st = reloc_check_params(q, g, m)) || (st = relocprior_check_params(pp))) return st;
+    return map_entry(
+        "relocprior", c, b, relocprior_reqs, [&] { return relocprior_check_overlap(b, g, q); },
+        [&] { return launch_relocprior(c, b, g, m, q, pp); });
 }
 
 // (the scratch is sized per call: a call in flight keeps the chunking it was launched with)

@@ -133,6 +133,8 @@ __device__ __forceinline__ void reloc_count(const uint32_t *pb, const uint32_t *
     }
 }
 
+// (relocprior_search_kernel, lslam_relocprior.h, holds a copy of the bitmap build, the n_occ / n_used block and
+// the staging loop below: a fix here is a fix there.  This kernel's code is pinned, so nothing is shared yet.)
 template <int FORM>
 __global__ __launch_bounds__(RELOC_TPB) void reloc_search_kernel(const RelocArgs a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -344,6 +346,8 @@ __global__ __launch_bounds__(RELOC_PEAK_TPB) void reloc_topk_kernel(const RelocA
     }
 }
 
+// (relocprior_select_kernel, lslam_relocprior.h, is a copy of this kernel behind its own eligibility test: a fix
+// to the winner, the rivals or the ambiguity test is a fix there too.)
 __global__ __launch_bounds__(64) void reloc_select_kernel(const RelocArgs a) {
     const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x), R = a.b.n_robots, K = a.K;
     if (r >= R) return;

@@ -35,9 +35,21 @@ the filter on the device; the others keep theirs::
     grid.upload(stored)                                        # a restart
     rel.relocalize(xy, scan_chunk_off, chunk_pt_off, grid=grid, lm=lm)
 
+Two priors narrow the coarse search to the candidates a robot can have (``lslam_map_relocalize_prior``):
+``field``, the ``DIST_NOT_FREE`` distance field of the grid, admits only coarse cells with free space in
+them, and rejects a refined pose that stands on a cell with less clearance than ``clear_min2``;
+``window``, a stale pose, admits only the cells within ``half_xy`` and the headings within ``half_theta``
+of it, so a filter that drifted a metre does not pay the whole-grid search, and the half-turn twin that
+the stale pose rules out is not a rival::
+
+    free = DistanceField(grid, mode=DIST_NOT_FREE)
+    free.step()
+    rel.relocalize(xy, scan_chunk_off, chunk_pt_off, grid=grid, lm=lm, field=free, window=lm.x)
+
 The definitions are the comments on ``lslam_map_match``, ``lslam_map_fuse`` and
-``lslam_map_relocalize`` in include/lidarslam.h; tests/mapmatch_ref.py, tests/mapfuse_ref.py and
-tests/reloc_ref.py are their NumPy forms and the kernels match them bit for bit, given the
+``lslam_map_relocalize`` (and ``lslam_map_relocalize_prior``) in include/lidarslam.h;
+tests/mapmatch_ref.py, tests/mapfuse_ref.py, tests/reloc_ref.py and tests/relocprior_ref.py are
+their NumPy forms and the kernels match them bit for bit, given the
 (cos, sin) that the library wrote to ``rot0``.
 """
 from __future__ import annotations
@@ -48,7 +60,7 @@ import numpy as np
 
 from . import _lib
 from .device import Context, DeviceArray
-from .mapping import OccupancyGrid
+from .mapping import DistanceField, OccupancyGrid
 from .odometry import _Grow, rot_table
 from .slam import LandmarkMap, MapInput
 
@@ -61,6 +73,7 @@ RELOC_LOST, RELOC_AMBIGUOUS = _lib.RELOC_LOST, _lib.RELOC_AMBIGUOUS
 _FUSE_KEYS = ("r_scale", "nis_max", "cut_permille")
 _RELOC_KEYS = ("head_step", "n_head", "factor", "n_cand", "ambig_permille", "dup_mm", "dup_rad", "reset_sigma_xy",
                "reset_sigma_theta")
+_PRIOR_KEYS = ("half_xy", "half_theta", "clear_min2")
 
 
 def head_table(n_head, head_step):
@@ -259,8 +272,9 @@ class GridRelocalizer:
     """R robots per call on one GPU.  ``params``: head_step, n_head, factor, n_cand, ambig_permille,
     dup_mm, dup_rad, reset_sigma_xy, reset_sigma_theta (``lslam_reloc_params``; defaults 2 pi / 180,
     180, 4, 8, 900, 100.0, 0.0873, 50.0, 0.05) and the fine matcher's (``lslam_mapmatch_params``, as
-    ``GridLocalizer``).  The cell size, the map's width and max_range are the grid's, given with each
-    call."""
+    ``GridLocalizer``), and for a call with ``field`` or ``window`` half_xy, half_theta, clear_min2
+    (``lslam_relocprior_params``; defaults 1000.0 mm, 0.5 rad, 16).  The cell size, the map's width and
+    max_range are the grid's, given with each call."""
 
     _PER_RANK = (("cand", 4, np.int32), ("cand_pose", 3, np.float64), ("fine_pose", 3, np.float64),
                  ("fine_delta", 3, np.float64), ("fine_best", 4, np.int32), ("fine_nvalid", 2, np.int32),
@@ -272,10 +286,14 @@ class GridRelocalizer:
             raise ValueError("n_robots must be > 0")
         self.ctx, self.R = ctx, R
         self.q = _lib.reloc_params(**{k: params.pop(k) for k in _RELOC_KEYS if k in params})
+        self.pp = _lib.relocprior_params(**{k: params.pop(k) for k in _PRIOR_KEYS if k in params})
         self.p = _lib.mapmatch_params(**params)
         # (a range error of params surfaces here, from the first call)
         _lib.check(_lib.load().lslam_map_relocalize(ctx.handle, C.byref(_lib.RelocBatch()), C.byref(_lib.grid_params()),
                                                     C.byref(self.p), C.byref(self.q)), "lslam_map_relocalize")
+        _lib.check(_lib.load().lslam_map_relocalize_prior(ctx.handle, C.byref(_lib.RelocPriorBatch()),
+                                                          C.byref(_lib.grid_params()), C.byref(self.p), C.byref(self.q),
+                                                          C.byref(self.pp)), "lslam_map_relocalize_prior")
         K = self.K = int(self.q.n_cand)
         self.rot_host = rot_table(self.p.k_theta, self.p.theta_step)
         self.rot = ctx.to_device(self.rot_host)
@@ -292,6 +310,8 @@ class GridRelocalizer:
         self._off = ctx.empty(R + 1, np.int32)
         self._have_coarse = False
         self._out, self._P_out = self.pose, None
+        self._prior = None  # a prior call's own buffers (n_admit, fine_clear2, the window), made by the first
+        self._have_prior = False
         self.calls = 0
 
     def set_budget(self, nbytes):
@@ -299,13 +319,33 @@ class GridRelocalizer:
         default).  No result depends on it."""
         _lib.check(_lib.load().lslam_set_reloc_budget(self.ctx.handle, int(nbytes)), "lslam_set_reloc_budget")
 
-    def relocalize(self, xy, scan_chunk_off=None, chunk_pt_off=None, grid=None, lm=None, want_coarse=False, sync=True):
+    def relocalize(self, xy, scan_chunk_off=None, chunk_pt_off=None, grid=None, lm=None, want_coarse=False, sync=True,
+                   field=None, window=None, prior=False):
         """One revolution per robot, in the forms ``GridLocalizer.step`` accepts; ``grid``: the
         ``OccupancyGrid`` to find the robots in.  With ``lm`` (a ``LandmarkMap``) the pose of a found,
         unambiguous robot is written over ``lm.x`` and diag(reset_sigma_xy^2, reset_sigma_xy^2,
         reset_sigma_theta^2) over its ``lm.P``; LOST and AMBIGUOUS robots keep the bits of both.
-        Without it the poses go to ``self.pose``, NaN where none was found."""
+        Without it the poses go to ``self.pose``, NaN where none was found.
+
+        ``field``: a ``DistanceField`` of ``grid`` in ``DIST_NOT_FREE`` mode, stepped, with
+        d_max^2 >= clear_min2: the free-space prior.  ``window`` [R, 3]: a stale pose (a host array, a
+        float64 ``DeviceArray`` such as ``lm.x``, or a ``LandmarkMap``), the centre of the search
+        window; it is read before ``lm.x`` is written.  With either the call is
+        ``lslam_map_relocalize_prior``; with neither it is ``lslam_map_relocalize`` as before, unless
+        ``prior`` asks for ``lslam_map_relocalize_prior`` all the same: the same results bit for bit, plus
+        ``n_admit`` (every cell, every heading) and ``fine_clear2`` (zeros)."""
         ctx, R, K = self.ctx, self.R, self.K
+        if field is not None:
+            if not isinstance(field, DistanceField):
+                raise ValueError("field must be a DistanceField")
+            if field.grid is not grid:
+                raise ValueError("field must be the distance field of grid")
+            if int(field.p.mode) != _lib.DIST_NOT_FREE:
+                raise ValueError("field must be a DIST_NOT_FREE distance field (mode=DIST_NOT_FREE)")
+            if int(field.p.d_max) ** 2 < int(self.pp.clear_min2):
+                raise ValueError("field saturates below clear_min2: d_max^2 must be >= clear_min2")
+            if not field.steps:
+                raise ValueError("no step yet: the field has not been computed")
         if lm is not None:
             if not isinstance(lm, LandmarkMap):
                 raise ValueError("lm must be a LandmarkMap")
@@ -334,18 +374,55 @@ class GridRelocalizer:
                 self.coarse = ctx.empty(shape, np.int32)
             b.coarse_scores = self.coarse.addr
         self._have_coarse = bool(want_coarse)
-        _lib.check(_lib.load().lslam_map_relocalize(ctx.handle, C.byref(b), C.byref(grid.p), C.byref(self.p),
-                                                    C.byref(self.q)), "lslam_map_relocalize")
+        self._have_prior = field is not None or window is not None or bool(prior)
+        if self._have_prior:
+            self._relocalize_prior(b, grid, field, window)
+        else:
+            _lib.check(_lib.load().lslam_map_relocalize(ctx.handle, C.byref(b), C.byref(grid.p), C.byref(self.p),
+                                                        C.byref(self.q)), "lslam_map_relocalize")
         self.calls += 1
         if sync:
             ctx.sync()
+
+    def _relocalize_prior(self, b, grid, field, window):
+        """``lslam_map_relocalize_prior`` with the filled ``RelocBatch`` b."""
+        ctx, R, K = self.ctx, self.R, self.K
+        if self._prior is None:
+            self._prior = {"n_admit": ctx.empty((R, 2), np.int32), "fine_clear2": ctx.empty((K, R), np.int32),
+                           "window": ctx.empty((R, 3), np.float64)}
+            for a in self._prior.values():
+                a.fill_zero()
+        pb = _lib.RelocPriorBatch()
+        pb.r = b
+        pb.n_admit, pb.fine_clear2 = self._prior["n_admit"].addr, self._prior["fine_clear2"].addr
+        if field is not None:
+            pb.clear_d2 = field.d2.addr
+        if window is not None:
+            if isinstance(window, LandmarkMap):
+                if window.R != R:
+                    raise ValueError("the map holds %d robots, the localizer %d" % (window.R, R))
+                window = window.x
+            if isinstance(window, DeviceArray):
+                if window.dtype != np.float64 or window.nbytes < 24 * R:
+                    raise ValueError("device window must be float64 [n_robots, 3]")
+                pb.win_pose = window.addr
+            else:
+                hw = np.ascontiguousarray(window, np.float64)
+                if hw.size != 3 * R:
+                    raise ValueError("window must hold n_robots x 3 values")
+                self._prior["window"].upload_async(hw.reshape(R, 3))
+                pb.win_pose = self._prior["window"].addr
+        _lib.check(_lib.load().lslam_map_relocalize_prior(ctx.handle, C.byref(pb), C.byref(grid.p), C.byref(self.p),
+                                                          C.byref(self.q), C.byref(self.pp)), "lslam_map_relocalize_prior")
 
     def results(self):
         """The last call's pose [R, 3] (``lm.x`` after a call with ``lm``), flags [R] (RELOC_*),
         result [R, 8] (winner rank, its k, ty, tx, coarse score, fine score, best rival's rank or -1,
         its fine score), n_occ [R], n_used [R], per rank j < K cand [K, R, 4], cand_pose [K, R, 3] and
         the fine matcher's fine_pose, fine_delta, fine_best, fine_nvalid, fine_rot0, fine_flags
-        [K, R, ..]; P [R, 3, 3] after a call with ``lm``; coarse_scores [R, n_head, Wc, Wc] when asked for."""
+        [K, R, ..]; P [R, 3, 3] after a call with ``lm``; coarse_scores [R, n_head, Wc, Wc] when asked for;
+        after a call with ``field`` or ``window`` n_admit [R, 2] (admissible coarse cells, admissible
+        headings) and fine_clear2 [K, R] (the field at each refined pose's cell)."""
         out = {"pose": self._out.download().reshape(-1, 3)[:self.R], "flags": self.flags.download(),
                "result": self.result.download(), "n_occ": self.n_occ.download(), "n_used": self.n_used.download()}
         for n, _, _ in self._PER_RANK:
@@ -354,4 +431,6 @@ class GridRelocalizer:
             out["P"] = self._P_out.download().reshape(-1, 3, 3)[:self.R]
         if self._have_coarse:
             out["coarse_scores"] = self.coarse.download()
+        if self._have_prior:
+            out["n_admit"], out["fine_clear2"] = self._prior["n_admit"].download(), self._prior["fine_clear2"].download()
         return out
