@@ -417,6 +417,13 @@ def check(status, what=""):
     return status
 
 
+def call(name, ctx, batch, *params):
+    """Entry point ``name`` on ``ctx`` with a batch and its parameter structs, each passed by reference
+    (None: NULL), the status checked under the entry point's name.  The by-reference is ctypes' own:
+    ``load`` declares those arguments as pointers, and a struct given for a pointer is passed so."""
+    return check(getattr(load(), name)(ctx.handle, batch, *params), name)
+
+
 def _params_factory(name, struct):
     """``name_params(**kw)``: the library's defaults for ``struct`` with the given fields set."""
     def make(**kw):

@@ -54,15 +54,14 @@ their NumPy forms and the kernels match them bit for bit, given the
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
+from . import _lib, staging
 from .device import Context, DeviceArray
 from .mapping import DistanceField, OccupancyGrid
-from .odometry import _Grow, rot_table
-from .slam import LandmarkMap, MapInput
+from .odometry import rot_table
+from .slam import LandmarkMap
+from .staging import Staging
 
 MAPMATCH_EMPTY, MAPMATCH_EDGE = _lib.MAPMATCH_EMPTY, _lib.MAPMATCH_EDGE
 MAPMATCH_BAD_POSE, MAPMATCH_WEAK = _lib.MAPMATCH_BAD_POSE, _lib.MAPMATCH_WEAK
@@ -83,6 +82,13 @@ def head_table(n_head, head_step):
     return np.ascontiguousarray(np.stack([np.cos(a), np.sin(a)], -1))
 
 
+def _check_grid(grid, R):
+    if not isinstance(grid, OccupancyGrid):
+        raise ValueError("grid is required (an OccupancyGrid)")
+    if grid.R != R:
+        raise ValueError("the grid holds %d robots, the localizer %d" % (grid.R, R))
+
+
 class GridLocalizer:
     """R robots per call on one GPU.  ``params``: theta_step, win_w, smear, k_trans, k_theta, occ_min,
     min_permille (``lslam_mapmatch_params``; defaults pi/360, 512, 2, 10, 20, 85, 500), and for
@@ -97,10 +103,8 @@ class GridLocalizer:
         self.fp = _lib.mapfuse_params(**{k: params.pop(k) for k in _FUSE_KEYS if k in params})
         self.p = _lib.mapmatch_params(**params)
         # (a range error of params surfaces here, from the first call)
-        _lib.check(_lib.load().lslam_map_match(ctx.handle, C.byref(_lib.MapMatchBatch()), C.byref(_lib.grid_params()),
-                                               C.byref(self.p)), "lslam_map_match")
-        _lib.check(_lib.load().lslam_map_fuse(ctx.handle, C.byref(_lib.MapFuseBatch()), C.byref(_lib.grid_params()),
-                                              C.byref(self.p), C.byref(self.fp)), "lslam_map_fuse")
+        _lib.call("lslam_map_match", ctx, _lib.MapMatchBatch(), _lib.grid_params(), self.p)
+        _lib.call("lslam_map_fuse", ctx, _lib.MapFuseBatch(), _lib.grid_params(), self.p, self.fp)
         self.Nt, self.Nth = 2 * self.p.k_trans + 1, 2 * self.p.k_theta + 1
         self.rot_host = rot_table(self.p.k_theta, self.p.theta_step)
         self.rot = ctx.to_device(self.rot_host)
@@ -113,43 +117,12 @@ class GridLocalizer:
         for a in (self.pose, self.delta, self.best, self.n_valid, self.rot0, self.flags):
             a.fill_zero()
         self.scores = None
-        self._xy = _Grow(ctx, np.float64)
-        self._off = ctx.empty(R + 1, np.int32)
-        self._guess = ctx.empty((R, 3), np.float64)
+        self._stage = Staging(ctx, R)
         self._have_scores = False
         self._out = self.pose
         self._fused = None  # fuse's buffers (P, z, Rm, nis, moments), made by the first fuse
         self._P_out = None
         self.steps = 0
-
-    def _revolutions(self, xy, scan_chunk_off, chunk_pt_off, grid):
-        """The checks of a step's revolutions and grid: (device xy, point offsets per robot)."""
-        R = self.R
-        if isinstance(xy, MapInput):
-            xy, scan_chunk_off, chunk_pt_off = xy.xy, xy.sco, xy.cpo
-        if not isinstance(grid, OccupancyGrid):
-            raise ValueError("grid is required (an OccupancyGrid)")
-        if grid.R != R:
-            raise ValueError("the grid holds %d robots, the localizer %d" % (grid.R, R))
-        sco = np.ascontiguousarray(scan_chunk_off, np.int64).reshape(-1)
-        cpo = np.ascontiguousarray(chunk_pt_off, np.int64).reshape(-1)
-        if sco.size != R + 1:
-            raise ValueError("one revolution per robot: scan_chunk_off needs n_robots + 1 entries")
-        off = cpo[sco]
-        p0, p1 = int(off[0]), int(off[-1])
-        if p0 < 0 or np.any(np.diff(off) < 0) or p1 >= 2 ** 31:
-            raise ValueError("inconsistent CSR offsets")
-        if isinstance(xy, DeviceArray):
-            if xy.dtype != np.float64 or xy.nbytes < 16 * p1:
-                raise ValueError("device xy must be float64 [n, 2] with n >= the last point offset")
-            dxy = xy
-        else:
-            h = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
-            if h.shape[0] < p1:
-                raise ValueError("xy holds fewer points than chunk_pt_off describes")
-            dxy = self._xy.put_host(h[p0:p1])
-            off = off - p0
-        return dxy, off
 
     def step(self, xy, scan_chunk_off=None, chunk_pt_off=None, grid=None, pose=None, write_back=False,
              want_scores=False, sync=True):
@@ -159,41 +132,24 @@ class GridLocalizer:
         (x, y, theta), the guess: a host array, a float64 ``DeviceArray`` or a ``LandmarkMap``
         (its ``x``).  ``write_back``: with a device pose, the result is written over it (a robot
         whose match is EMPTY, WEAK or BAD_POSE keeps its bits); otherwise it goes to ``self.pose``."""
-        R = self.R
-        if pose is None and isinstance(grid, OccupancyGrid) and grid.R == R:  # (the grid's errors come first)
-            raise ValueError("pose is required (host [R, 3], a DeviceArray or a LandmarkMap)")
-        dxy, off = self._revolutions(xy, scan_chunk_off, chunk_pt_off, grid)
-        if isinstance(pose, LandmarkMap):
-            if pose.R != R:
-                raise ValueError("the map holds %d robots, the localizer %d" % (pose.R, R))
-            pose = pose.x
-        if isinstance(pose, DeviceArray):
-            if pose.dtype != np.float64 or pose.nbytes < 24 * R:
-                raise ValueError("device pose must be float64 [n_robots, 3]")
-            dpose = pose
-        else:
-            if write_back:
-                raise ValueError("write_back needs a device pose (a DeviceArray or a LandmarkMap)")
-            hp = np.ascontiguousarray(pose, np.float64)
-            if hp.size != 3 * R:
-                raise ValueError("pose must hold n_robots x 3 values")
-            dpose = self._guess
-            dpose.upload_async(hp.reshape(R, 3))
+        _check_grid(grid, self.R)  # (the grid's errors come first)
+        staging.require_pose(pose)
+        dxy, doff = self._stage.revolution(xy, scan_chunk_off, chunk_pt_off)
+        if write_back and not isinstance(pose, (DeviceArray, LandmarkMap)):
+            raise ValueError("write_back needs a device pose (a DeviceArray or a LandmarkMap)")
+        dpose = self._stage.pose(pose, "localizer")
         dout = dpose if write_back else self.pose
         b = _lib.MapMatchBatch()
-        self._fill(b, dxy, off, dpose, dout, grid, want_scores)
+        self._fill(b, dxy, doff, dpose, dout, grid, want_scores)
         self._P_out = None
-        _lib.check(_lib.load().lslam_map_match(self.ctx.handle, C.byref(b), C.byref(grid.p), C.byref(self.p)),
-                   "lslam_map_match")
+        _lib.call("lslam_map_match", self.ctx, b, grid.p, self.p)
         self.steps += 1
         if sync:
             self.ctx.sync()
 
-    def _fill(self, b, dxy, off, dpose, dout, grid, want_scores):
+    def _fill(self, b, dxy, doff, dpose, dout, grid, want_scores):
         """The fields of a ``MapMatchBatch`` for one call."""
         R = self.R
-        doff = self._off
-        doff.upload_async(np.ascontiguousarray(off, np.int32))
         b.n_robots = R
         b.xy, b.pt_off, b.pose, b.origin = dxy.addr, doff.addr, dpose.addr, grid.origin.addr
         b.logodds, b.rot = grid.logodds.addr, self.rot.addr
@@ -215,21 +171,9 @@ class GridLocalizer:
         only read.  A robot whose match is EMPTY, WEAK, BAD_POSE, OUTLIER or BAD_COV keeps the bits
         of its mean and covariance."""
         ctx, R = self.ctx, self.R
-        if lm is not None:
-            if x is not None or P is not None:
-                raise ValueError("give lm, or x and P")
-            if not isinstance(lm, LandmarkMap):
-                raise ValueError("lm must be a LandmarkMap")
-            if lm.R != R:
-                raise ValueError("the map holds %d robots, the localizer %d" % (lm.R, R))
-            x, P = lm.x, lm.P
-        if not isinstance(x, DeviceArray) or not isinstance(P, DeviceArray):
-            raise ValueError("fuse needs the filter on the device: lm (a LandmarkMap), or x and P (DeviceArrays)")
-        if x.dtype != np.float64 or x.nbytes < 24 * R:
-            raise ValueError("device x must be float64 [n_robots, 3]")
-        if P.dtype != np.float64 or P.nbytes < 72 * R:
-            raise ValueError("device P must be float64 [n_robots, 9]")
-        dxy, off = self._revolutions(xy, scan_chunk_off, chunk_pt_off, grid)
+        x, P = staging.filter_arguments(lm, x, P, R, "localizer")
+        _check_grid(grid, R)
+        dxy, doff = self._stage.revolution(xy, scan_chunk_off, chunk_pt_off)
         if self._fused is None:
             self._fused = {"P": ctx.empty((R, 9), np.float64), "z": ctx.empty((R, 3), np.float64),
                            "Rm": ctx.empty((R, 9), np.float64), "nis": ctx.empty(R, np.float64),
@@ -238,12 +182,11 @@ class GridLocalizer:
                 a.fill_zero()
         fb = self._fused
         b = _lib.MapFuseBatch()
-        self._fill(b.m, dxy, off, x, x if write_back else self.pose, grid, want_scores)
+        self._fill(b.m, dxy, doff, x, x if write_back else self.pose, grid, want_scores)
         self._P_out = P if write_back else fb["P"]
         b.P, b.P_out = P.addr, self._P_out.addr
         b.z, b.Rm, b.nis, b.moments = fb["z"].addr, fb["Rm"].addr, fb["nis"].addr, fb["moments"].addr
-        _lib.check(_lib.load().lslam_map_fuse(ctx.handle, C.byref(b), C.byref(grid.p), C.byref(self.p), C.byref(self.fp)),
-                   "lslam_map_fuse")
+        _lib.call("lslam_map_fuse", ctx, b, grid.p, self.p, self.fp)
         self.steps += 1
         if sync:
             ctx.sync()
@@ -289,11 +232,8 @@ class GridRelocalizer:
         self.pp = _lib.relocprior_params(**{k: params.pop(k) for k in _PRIOR_KEYS if k in params})
         self.p = _lib.mapmatch_params(**params)
         # (a range error of params surfaces here, from the first call)
-        _lib.check(_lib.load().lslam_map_relocalize(ctx.handle, C.byref(_lib.RelocBatch()), C.byref(_lib.grid_params()),
-                                                    C.byref(self.p), C.byref(self.q)), "lslam_map_relocalize")
-        _lib.check(_lib.load().lslam_map_relocalize_prior(ctx.handle, C.byref(_lib.RelocPriorBatch()),
-                                                          C.byref(_lib.grid_params()), C.byref(self.p), C.byref(self.q),
-                                                          C.byref(self.pp)), "lslam_map_relocalize_prior")
+        _lib.call("lslam_map_relocalize", ctx, _lib.RelocBatch(), _lib.grid_params(), self.p, self.q)
+        _lib.call("lslam_map_relocalize_prior", ctx, _lib.RelocPriorBatch(), _lib.grid_params(), self.p, self.q, self.pp)
         K = self.K = int(self.q.n_cand)
         self.rot_host = rot_table(self.p.k_theta, self.p.theta_step)
         self.rot = ctx.to_device(self.rot_host)
@@ -306,8 +246,7 @@ class GridRelocalizer:
         for a in (self.n_occ, self.n_used, self.result, self.flags) + tuple(self.ranks.values()):
             a.fill_zero()
         self.coarse = None
-        self._xy = _Grow(ctx, np.float64)
-        self._off = ctx.empty(R + 1, np.int32)
+        self._stage = Staging(ctx, R, pose=False)  # (the window's buffer comes with the first prior call's)
         self._have_coarse = False
         self._out, self._P_out = self.pose, None
         self._prior = None  # a prior call's own buffers (n_admit, fine_clear2, the window), made by the first
@@ -317,7 +256,7 @@ class GridRelocalizer:
     def set_budget(self, nbytes):
         """Bytes of coarse-score scratch per chunk of robots (``lslam_set_reloc_budget``; <= 0: the
         default).  No result depends on it."""
-        _lib.check(_lib.load().lslam_set_reloc_budget(self.ctx.handle, int(nbytes)), "lslam_set_reloc_budget")
+        _lib.call("lslam_set_reloc_budget", self.ctx, int(nbytes))
 
     def relocalize(self, xy, scan_chunk_off=None, chunk_pt_off=None, grid=None, lm=None, want_coarse=False, sync=True,
                    field=None, window=None, prior=False):
@@ -351,11 +290,11 @@ class GridRelocalizer:
                 raise ValueError("lm must be a LandmarkMap")
             if lm.R != R:
                 raise ValueError("the map holds %d robots, the localizer %d" % (lm.R, R))
-        dxy, off = GridLocalizer._revolutions(self, xy, scan_chunk_off, chunk_pt_off, grid)
-        self._off.upload_async(np.ascontiguousarray(off, np.int32))
+        _check_grid(grid, R)
+        dxy, doff = self._stage.revolution(xy, scan_chunk_off, chunk_pt_off)
         b = _lib.RelocBatch()
         b.n_robots = R
-        b.xy, b.pt_off, b.origin, b.logodds = dxy.addr, self._off.addr, grid.origin.addr, grid.logodds.addr
+        b.xy, b.pt_off, b.origin, b.logodds = dxy.addr, doff.addr, grid.origin.addr, grid.logodds.addr
         b.rot, b.head_rot = self.rot.addr, self.head_rot.addr
         b.n_occ, b.n_used, b.result, b.flags = self.n_occ.addr, self.n_used.addr, self.result.addr, self.flags.addr
         for n, _, _ in self._PER_RANK:
@@ -378,8 +317,7 @@ class GridRelocalizer:
         if self._have_prior:
             self._relocalize_prior(b, grid, field, window)
         else:
-            _lib.check(_lib.load().lslam_map_relocalize(ctx.handle, C.byref(b), C.byref(grid.p), C.byref(self.p),
-                                                        C.byref(self.q)), "lslam_map_relocalize")
+            _lib.call("lslam_map_relocalize", ctx, b, grid.p, self.p, self.q)
         self.calls += 1
         if sync:
             ctx.sync()
@@ -392,28 +330,15 @@ class GridRelocalizer:
                            "window": ctx.empty((R, 3), np.float64)}
             for a in self._prior.values():
                 a.fill_zero()
+            self._stage.pose_buf = self._prior["window"]
         pb = _lib.RelocPriorBatch()
         pb.r = b
         pb.n_admit, pb.fine_clear2 = self._prior["n_admit"].addr, self._prior["fine_clear2"].addr
         if field is not None:
             pb.clear_d2 = field.d2.addr
         if window is not None:
-            if isinstance(window, LandmarkMap):
-                if window.R != R:
-                    raise ValueError("the map holds %d robots, the localizer %d" % (window.R, R))
-                window = window.x
-            if isinstance(window, DeviceArray):
-                if window.dtype != np.float64 or window.nbytes < 24 * R:
-                    raise ValueError("device window must be float64 [n_robots, 3]")
-                pb.win_pose = window.addr
-            else:
-                hw = np.ascontiguousarray(window, np.float64)
-                if hw.size != 3 * R:
-                    raise ValueError("window must hold n_robots x 3 values")
-                self._prior["window"].upload_async(hw.reshape(R, 3))
-                pb.win_pose = self._prior["window"].addr
-        _lib.check(_lib.load().lslam_map_relocalize_prior(ctx.handle, C.byref(pb), C.byref(grid.p), C.byref(self.p),
-                                                          C.byref(self.q), C.byref(self.pp)), "lslam_map_relocalize_prior")
+            pb.win_pose = self._stage.pose(window, "localizer", "window").addr
+        _lib.call("lslam_map_relocalize_prior", ctx, pb, grid.p, self.p, self.q, self.pp)
 
     def results(self):
         """The last call's pose [R, 3] (``lm.x`` after a call with ``lm``), flags [R] (RELOC_*),

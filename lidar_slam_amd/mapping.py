@@ -22,10 +22,9 @@ import ctypes as C
 
 import numpy as np
 
-from . import _lib
+from . import _lib, staging
 from .device import Context, DeviceArray
-from .odometry import _Grow
-from .slam import LandmarkMap, MapInput
+from .staging import Staging, _Grow
 
 GRID_BAD_POSE, GRID_CLIPPED = _lib.GRID_BAD_POSE, _lib.GRID_CLIPPED
 RECENTRE_BAD_POSE, RECENTRE_MOVED, RECENTRE_CLEARED = _lib.RECENTRE_BAD_POSE, _lib.RECENTRE_MOVED, _lib.RECENTRE_CLEARED
@@ -49,58 +48,6 @@ def recentre_band_rows(grid_w):
     return max(1, min(int(grid_w), 16384 // int(grid_w)))
 
 
-def _stage_pose(owner, pose):
-    """The pose forms of ``OccupancyGrid.step`` -> a device [R, 3] float64."""
-    R = owner.R
-    if pose is None:
-        raise ValueError("pose is required (host [R, 3], a DeviceArray or a LandmarkMap)")
-    if isinstance(pose, LandmarkMap):
-        if pose.R != R:
-            raise ValueError("the map holds %d robots, the grid %d" % (pose.R, R))
-        pose = pose.x
-    if isinstance(pose, DeviceArray):
-        if pose.dtype != np.float64 or pose.nbytes < 24 * R:
-            raise ValueError("device pose must be float64 [n_robots, 3]")
-        return pose
-    hp = np.ascontiguousarray(pose, np.float64)
-    if hp.size != 3 * R:
-        raise ValueError("pose must hold n_robots x 3 values")
-    owner._pose.upload_async(hp.reshape(R, 3))
-    return owner._pose
-
-
-def _stage_revolution(owner, xy, scan_chunk_off, chunk_pt_off, pose):
-    """The argument forms of ``OccupancyGrid.step`` -> device (xy, pt_off, pose).  ``owner`` holds ctx,
-    R and the staging buffers _xy, _off, _pose."""
-    R = owner.R
-    if isinstance(xy, MapInput):
-        xy, scan_chunk_off, chunk_pt_off = xy.xy, xy.sco, xy.cpo
-    if pose is None:
-        raise ValueError("pose is required (host [R, 3], a DeviceArray or a LandmarkMap)")
-    sco = np.ascontiguousarray(scan_chunk_off, np.int64).reshape(-1)
-    cpo = np.ascontiguousarray(chunk_pt_off, np.int64).reshape(-1)
-    if sco.size != R + 1:
-        raise ValueError("one revolution per robot: scan_chunk_off needs n_robots + 1 entries")
-    off = cpo[sco]
-    p0, p1 = int(off[0]), int(off[-1])
-    if p0 < 0 or np.any(np.diff(off) < 0) or p1 >= 2 ** 31:
-        raise ValueError("inconsistent CSR offsets")
-    if isinstance(xy, DeviceArray):
-        if xy.dtype != np.float64 or xy.nbytes < 16 * p1:
-            raise ValueError("device xy must be float64 [n, 2] with n >= the last point offset")
-        dxy = xy
-    else:
-        h = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
-        if h.shape[0] < p1:
-            raise ValueError("xy holds fewer points than chunk_pt_off describes")
-        dxy = owner._xy.put_host(h[p0:p1])
-        off = off - p0
-    dpose = _stage_pose(owner, pose)
-    owner._off.upload_async(np.ascontiguousarray(off, np.int32))
-    owner._off_host = np.ascontiguousarray(off, np.int64)
-    return dxy, owner._off, dpose
-
-
 class OccupancyGrid:
     """R robots' grids on one GPU.  ``params``: cell, max_range, grid_w, l_hit, l_miss, l_min, l_max
     (``lslam_grid_params``; defaults 20 mm, 8000 mm, 512, 85, -41, -200, 350; log-odds in 0.01 nat).
@@ -120,8 +67,7 @@ class OccupancyGrid:
         self._origin_host = np.ascontiguousarray(np.broadcast_to(o, (R, 2)), np.float64)
         self._origin_stale = False  # a recentre may have moved the device's origin since the last read
         # (a range error of params surfaces here, from the first call, before anything large is allocated)
-        _lib.check(_lib.load().lslam_grid_update(ctx.handle, C.byref(_lib.GridBatch()), C.byref(self.p)),
-                   "lslam_grid_update")
+        _lib.call("lslam_grid_update", ctx, _lib.GridBatch(), self.p)
         self.origin = ctx.to_device(self._origin_host)
         self.logodds = ctx.empty((R, self.W, self.W), np.int16)
         self.logodds.fill_zero()
@@ -130,9 +76,7 @@ class OccupancyGrid:
         self.flags = ctx.empty(R, np.int32)
         for a in (self.rot, self.n_used, self.flags):
             a.fill_zero()
-        self._xy = _Grow(ctx, np.float64)
-        self._off = ctx.empty(R + 1, np.int32)  # (uploads are ordered on the stream: a step in flight keeps its own)
-        self._pose = ctx.empty((R, 3), np.float64)
+        self._stage = Staging(ctx, R)
         self.steps = 0
         self._shift = self._rflags = None  # recentre's outputs, allocated by its first call
 
@@ -159,12 +103,14 @@ class OccupancyGrid:
         is ordered on the context's stream, before whatever overwrites them later.  ``pose``
         [R, 3] (x, y, theta): a host array, a float64 ``DeviceArray`` (``lm.x``) or a ``LandmarkMap``."""
         ctx, R = self.ctx, self.R
-        dxy, doff, dpose = _stage_revolution(self, xy, scan_chunk_off, chunk_pt_off, pose)
+        staging.require_pose(pose)
+        dxy, doff = self._stage.revolution(xy, scan_chunk_off, chunk_pt_off)
+        dpose = self._stage.pose(pose, "grid")
         b = _lib.GridBatch()
         b.n_robots = R
         b.xy, b.pt_off, b.pose, b.origin = dxy.addr, doff.addr, dpose.addr, self.origin.addr
         b.logodds, b.rot, b.n_used, b.flags = self.logodds.addr, self.rot.addr, self.n_used.addr, self.flags.addr
-        _lib.check(_lib.load().lslam_grid_update(ctx.handle, C.byref(b), C.byref(self.p)), "lslam_grid_update")
+        _lib.call("lslam_grid_update", ctx, b, self.p)
         self.steps += 1
         if sync:
             ctx.sync()
@@ -179,15 +125,14 @@ class OccupancyGrid:
         ctx, R = self.ctx, self.R
         kw = {k: int(v) for k, v in (("margin", margin), ("quantum", quantum)) if v is not None}
         q = _lib.recentre_params(**kw)
-        dpose = _stage_pose(self, pose)
+        dpose = self._stage.pose(pose, "grid")
         if self._shift is None:
             self._shift, self._rflags = ctx.empty((R, 2), np.int32), ctx.empty(R, np.int32)
         b = _lib.RecentreBatch()
         b.n_robots = R
         b.pose, b.origin, b.logodds = dpose.addr, self.origin.addr, self.logodds.addr
         b.shift, b.flags = self._shift.addr, self._rflags.addr
-        _lib.check(_lib.load().lslam_grid_recentre(ctx.handle, C.byref(b), C.byref(self.p), C.byref(q)),
-                   "lslam_grid_recentre")
+        _lib.call("lslam_grid_recentre", ctx, b, self.p, q)
         self._origin_stale = True
         if sync:
             ctx.sync()
@@ -240,18 +185,15 @@ class GridRayCaster:
         ctx, R = self.ctx, self.R
         self.p = _lib.raycast_params(**params)
         # (a range error of params surfaces here, before anything is allocated)
-        _lib.check(_lib.load().lslam_grid_raycast(ctx.handle, C.byref(_lib.RaycastBatch()), C.byref(grid.p),
-                                                  C.byref(self.p)), "lslam_grid_raycast")
+        _lib.call("lslam_grid_raycast", ctx, _lib.RaycastBatch(), grid.p, self.p)
         self.counts = ctx.empty((R, 8), np.int32)
         self.rot = ctx.empty((R, 2), np.float64)
         self.flags = ctx.empty(R, np.int32)
         for a in (self.counts, self.rot, self.flags):
             a.fill_zero()
         self._cls, self._stop = _Grow(ctx, np.uint8), _Grow(ctx, np.int32)
-        self._xy = _Grow(ctx, np.float64)
-        self._off = ctx.empty(R + 1, np.int32)
-        self._pose = ctx.empty((R, 3), np.float64)
-        self._off_host = np.zeros(R + 1, np.int64)
+        self._stage = Staging(ctx, R)
+        self._span = (0, 0)  # the last step's points in _cls and _stop: the first and the last point offset
         self.steps = 0
 
     def step(self, xy, scan_chunk_off=None, chunk_pt_off=None, pose=None, sync=True, want_stop=True):
@@ -259,17 +201,18 @@ class GridRayCaster:
         a host array, a float64 ``DeviceArray`` (``lm.x``) or a ``LandmarkMap``.  ``want_stop=False``
         leaves the stop cells out (``stop`` NULL): classes and counts only."""
         ctx, R, g = self.ctx, self.R, self.grid
-        dxy, doff, dpose = _stage_revolution(self, xy, scan_chunk_off, chunk_pt_off, pose)
-        P = int(self._off_host[-1])
+        staging.require_pose(pose)
+        dxy, doff = self._stage.revolution(xy, scan_chunk_off, chunk_pt_off)
+        dpose = self._stage.pose(pose, "grid")
+        lo, P = int(self._stage.off_host[0]), int(self._stage.off_host[-1])
         b = _lib.RaycastBatch()
         b.n_robots = R
         b.xy, b.pt_off, b.pose, b.origin, b.logodds = dxy.addr, doff.addr, dpose.addr, g.origin.addr, g.logodds.addr
         b.cls = self._cls.reserve(P).addr
         b.stop = self._stop.reserve(3 * P).addr if want_stop else None
         b.counts, b.rot, b.flags = self.counts.addr, self.rot.addr, self.flags.addr
-        _lib.check(_lib.load().lslam_grid_raycast(ctx.handle, C.byref(b), C.byref(g.p), C.byref(self.p)),
-                   "lslam_grid_raycast")
-        self._has_stop = bool(want_stop)
+        _lib.call("lslam_grid_raycast", ctx, b, g.p, self.p)
+        self._span, self._has_stop = (lo, P), bool(want_stop)  # (kept from the call that wrote them: a refused step leaves both)
         self.steps += 1
         if sync:
             ctx.sync()
@@ -279,8 +222,7 @@ class GridRayCaster:
         out = np.empty((hi - lo) * width, grow.dtype)
         if out.nbytes:
             src = C.c_void_p(grow.buf.addr + lo * width * grow.dtype.itemsize)
-            _lib.check(self.ctx._L.lslam_d2h(self.ctx.handle, out.ctypes.data_as(C.c_void_p), src, out.nbytes),
-                       "lslam_d2h")
+            _lib.call("lslam_d2h", self.ctx, out.ctypes.data_as(C.c_void_p), src, out.nbytes)
         self.ctx.sync()
         return out
 
@@ -290,7 +232,7 @@ class GridRayCaster:
         the order of the revolution, robot after robot."""
         if not self.steps:
             raise ValueError("no step yet")
-        lo, hi = int(self._off_host[0]), int(self._off_host[-1])
+        lo, hi = self._span
         raw = self._head(self._cls, lo, hi)
         stop = self._head(self._stop, lo, hi, 3).reshape(-1, 3) if self._has_stop else None
         return {"cls": raw & 15, "kind": raw >> 4, "stop": stop, "counts": self.counts.download(),
@@ -307,7 +249,7 @@ class GridRayCaster:
 
     def novel_mask(self):
         """bool [P]: the returns inside space the map holds free, the dynamic-object mask."""
-        lo, hi = int(self._off_host[0]), int(self._off_host[-1])
+        lo, hi = self._span
         return (self._head(self._cls, lo, hi) & 15) == _lib.RAYCAST_NOVEL
 
     def inconsistency(self):
@@ -371,15 +313,10 @@ class DistanceField:
         self.a = _lib.fieldalign_params(**ak)
         self.f = _lib.fieldfuse_params(**fk)
         # (a range error of params surfaces here, before anything large is allocated)
-        L = _lib.load()
-        _lib.check(L.lslam_grid_distance(ctx.handle, C.byref(_lib.DistBatch()), C.byref(grid.p), C.byref(self.p)),
-                   "lslam_grid_distance")
-        _lib.check(L.lslam_field_score(ctx.handle, C.byref(_lib.FieldScoreBatch()), C.byref(grid.p), C.byref(self.q)),
-                   "lslam_field_score")
-        _lib.check(L.lslam_field_align(ctx.handle, C.byref(_lib.FieldAlignBatch()), C.byref(grid.p), C.byref(self.a)),
-                   "lslam_field_align")
-        _lib.check(L.lslam_field_fuse(ctx.handle, C.byref(_lib.FieldFuseBatch()), C.byref(grid.p), C.byref(self.a),
-                                      C.byref(self.f)), "lslam_field_fuse")
+        _lib.call("lslam_grid_distance", ctx, _lib.DistBatch(), grid.p, self.p)
+        _lib.call("lslam_field_score", ctx, _lib.FieldScoreBatch(), grid.p, self.q)
+        _lib.call("lslam_field_align", ctx, _lib.FieldAlignBatch(), grid.p, self.a)
+        _lib.call("lslam_field_fuse", ctx, _lib.FieldFuseBatch(), grid.p, self.a, self.f)
         self.d2 = ctx.empty((R, W, W), np.uint16)
         self.n_src = ctx.empty(R, np.int32)
         self.flags = ctx.empty(R, np.int32)
@@ -389,10 +326,7 @@ class DistanceField:
         self.score_flags = ctx.empty(R, np.int32)
         for a in (self.n_src, self.flags, self.rot, self.stats, self.clear2, self.score_flags):
             a.fill_zero()
-        self._xy = _Grow(ctx, np.float64)
-        self._off = ctx.empty(R + 1, np.int32)
-        self._pose = ctx.empty((R, 3), np.float64)
-        self._off_host = np.zeros(R + 1, np.int64)
+        self._stage = Staging(ctx, R)
         self.steps = self.scores = self.aligns = 0
         self._align = None  # align's outputs, allocated by its first call
         self._fuse = None   # fuse's own, likewise
@@ -404,8 +338,7 @@ class DistanceField:
         b = _lib.DistBatch()
         b.n_robots = self.R
         b.logodds, b.d2, b.n_src, b.flags = g.logodds.addr, self.d2.addr, self.n_src.addr, self.flags.addr
-        _lib.check(_lib.load().lslam_grid_distance(ctx.handle, C.byref(b), C.byref(g.p), C.byref(self.p)),
-                   "lslam_grid_distance")
+        _lib.call("lslam_grid_distance", ctx, b, g.p, self.p)
         self.steps += 1
         if sync:
             ctx.sync()
@@ -417,13 +350,14 @@ class DistanceField:
         if not self.steps:
             raise ValueError("no step yet: the field has not been computed")
         ctx, g = self.ctx, self.grid
-        dxy, doff, dpose = _stage_revolution(self, xy, scan_chunk_off, chunk_pt_off, pose)
+        staging.require_pose(pose)
+        dxy, doff = self._stage.revolution(xy, scan_chunk_off, chunk_pt_off)
+        dpose = self._stage.pose(pose, "grid")
         b = _lib.FieldScoreBatch()
         b.n_robots = self.R
         b.xy, b.pt_off, b.pose, b.origin, b.d2 = dxy.addr, doff.addr, dpose.addr, g.origin.addr, self.d2.addr
         b.rot, b.stats, b.clear2, b.flags = self.rot.addr, self.stats.addr, self.clear2.addr, self.score_flags.addr
-        _lib.check(_lib.load().lslam_field_score(ctx.handle, C.byref(b), C.byref(g.p), C.byref(self.q)),
-                   "lslam_field_score")
+        _lib.call("lslam_field_score", ctx, b, g.p, self.q)
         self.scores += 1
         if sync:
             ctx.sync()
@@ -442,14 +376,15 @@ class DistanceField:
             pose_out = o["pose_out"]
         if not isinstance(pose_out, DeviceArray) or pose_out.dtype != np.float64 or pose_out.nbytes < 24 * R:
             raise ValueError("pose_out must be a float64 DeviceArray [n_robots, 3]")
-        dxy, doff, dpose = _stage_revolution(self, xy, scan_chunk_off, chunk_pt_off, pose)
+        staging.require_pose(pose)
+        dxy, doff = self._stage.revolution(xy, scan_chunk_off, chunk_pt_off)
+        dpose = self._stage.pose(pose, "grid")
         b = _lib.FieldAlignBatch()
         b.n_robots = R
         b.xy, b.pt_off, b.pose, b.origin, b.d2 = dxy.addr, doff.addr, dpose.addr, g.origin.addr, self.d2.addr
         b.pose_out, b.trace, b.normal = pose_out.addr, o["trace"].addr, o["normal"].addr
         b.n_used, b.iters, b.flags = o["n_used"].addr, o["iters"].addr, o["flags"].addr
-        _lib.check(_lib.load().lslam_field_align(ctx.handle, C.byref(b), C.byref(g.p), C.byref(self.a)),
-                   "lslam_field_align")
+        _lib.call("lslam_field_align", ctx, b, g.p, self.a)
         self._align_out, self._align_rows, self._fused = pose_out, int(self.a.n_iter) + 1, False
         self.aligns += 1
         if sync:
@@ -476,37 +411,23 @@ class DistanceField:
         if not self.steps:
             raise ValueError("no step yet: the field has not been computed")
         ctx, g, R = self.ctx, self.grid, self.R
-        if lm is not None:
-            if x is not None or P is not None:
-                raise ValueError("give lm, or x and P")
-            if not isinstance(lm, LandmarkMap):
-                raise ValueError("lm must be a LandmarkMap")
-            if lm.R != R:
-                raise ValueError("the map holds %d robots, the grid %d" % (lm.R, R))
-            x, P = lm.x, lm.P
-        if not isinstance(x, DeviceArray) or not isinstance(P, DeviceArray):
-            raise ValueError("fuse needs the filter on the device: lm (a LandmarkMap), or x and P (DeviceArrays)")
-        if x.dtype != np.float64 or x.nbytes < 24 * R:
-            raise ValueError("device x must be float64 [n_robots, 3]")
-        if P.dtype != np.float64 or P.nbytes < 72 * R:
-            raise ValueError("device P must be float64 [n_robots, 9]")
+        x, P = staging.filter_arguments(lm, x, P, R, "grid")
         o = self._align_buffers()
         if self._fuse is None:
             self._fuse = dict(P=ctx.empty((R, 9), np.float64), z=ctx.empty((R, 3), np.float64),
                               info=ctx.empty((R, 9), np.float64), info_f=ctx.empty((R, 9), np.float64),
                               s2=ctx.empty(R, np.float64), nis=ctx.empty(R, np.float64))
         fo = self._fuse
-        dxy, doff, dpose = _stage_revolution(self, xy, scan_chunk_off, chunk_pt_off, x)
+        dxy, doff = self._stage.revolution(xy, scan_chunk_off, chunk_pt_off)
         pose_out, P_out = (x, P) if write_back else (o["pose_out"], fo["P"])
         b = _lib.FieldFuseBatch()
         b.a.n_robots = R
-        b.a.xy, b.a.pt_off, b.a.pose, b.a.origin, b.a.d2 = dxy.addr, doff.addr, dpose.addr, g.origin.addr, self.d2.addr
+        b.a.xy, b.a.pt_off, b.a.pose, b.a.origin, b.a.d2 = dxy.addr, doff.addr, x.addr, g.origin.addr, self.d2.addr
         b.a.pose_out, b.a.trace, b.a.normal = pose_out.addr, o["trace"].addr, o["normal"].addr
         b.a.n_used, b.a.iters, b.a.flags = o["n_used"].addr, o["iters"].addr, o["flags"].addr
         b.P, b.P_out, b.z = P.addr, P_out.addr, fo["z"].addr
         b.info, b.info_f, b.s2, b.nis = fo["info"].addr, fo["info_f"].addr, fo["s2"].addr, fo["nis"].addr
-        _lib.check(_lib.load().lslam_field_fuse(ctx.handle, C.byref(b), C.byref(g.p), C.byref(self.a), C.byref(self.f)),
-                   "lslam_field_fuse")
+        _lib.call("lslam_field_fuse", ctx, b, g.p, self.a, self.f)
         self._align_out, self._align_rows, self._fused, self._P_out = pose_out, int(self.a.n_iter) + 1, True, P_out
         self.aligns += 1
         if sync:

@@ -18,13 +18,11 @@ include/lidarslam.h; tests/scanmatch_ref.py is its NumPy form and the kernels ma
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import numpy as np
 
-from . import _lib
+from . import _lib, staging
 from .device import Context, DeviceArray
-from .slam import MapInput
+from .staging import _Grow, _as_device
 
 MATCH_EMPTY, MATCH_EDGE = _lib.MATCH_EMPTY, _lib.MATCH_EDGE
 
@@ -34,41 +32,6 @@ def rot_table(k_theta, theta_step):
     computes these itself: the caller's bits are the definition."""
     a = (np.arange(2 * int(k_theta) + 1) - int(k_theta)) * float(theta_step)
     return np.ascontiguousarray(np.stack([np.cos(a), np.sin(a)], -1))
-
-
-class _Grow:
-    """A grow-only device buffer of one dtype, filled from host arrays or device arrays."""
-
-    def __init__(self, ctx, dtype):
-        self.ctx, self.dtype, self.buf = ctx, np.dtype(dtype), None
-
-    def reserve(self, n):
-        if self.buf is None or self.buf.shape[0] < n:
-            self.ctx.sync()  # work in flight may still use the old allocation
-            self.buf = self.ctx.empty(max(int(n), 1), self.dtype)
-        return self.buf
-
-    def put_host(self, arr):
-        arr = np.ascontiguousarray(arr, self.dtype).reshape(-1)
-        b = self.reserve(arr.size)
-        if arr.nbytes:
-            _lib.check(self.ctx._L.lslam_h2d(self.ctx.handle, b.ptr, arr.ctypes.data_as(C.c_void_p), arr.nbytes),
-                       "lslam_h2d")
-            self.ctx._inflight.append(arr)
-            self.ctx.sync()  # arr may be a temporary
-        return b
-
-
-def _as_device(grow, x, dtype, min_items):
-    """x (host array or DeviceArray) -> a DeviceArray holding at least min_items items of dtype."""
-    if isinstance(x, DeviceArray):
-        if x.dtype != np.dtype(dtype) or x.nbytes < min_items * np.dtype(dtype).itemsize:
-            raise ValueError("device array must be %s with at least %d items" % (np.dtype(dtype), min_items))
-        return x
-    h = np.ascontiguousarray(x, dtype).reshape(-1)
-    if h.size < min_items:
-        raise ValueError("array holds %d items, %d needed" % (h.size, min_items))
-    return grow.put_host(h)
 
 
 class ScanMatcher:
@@ -124,7 +87,6 @@ class ScanMatcher:
                 self.scores = self.ctx.empty((R, self.Nth, self.Nt, self.Nt), np.int32)
             b.scores = self.scores.addr
         self._have_scores = bool(want_scores)
-        up = None
         if ukf is not None:
             if u_out is None:
                 if self.u is None:
@@ -133,11 +95,10 @@ class ScanMatcher:
             if u_out.dtype != np.float64 or u_out.nbytes < 16 * R:
                 raise ValueError("u_out must be float64 [n_robots, 2]")
             b.ukf_u = u_out.addr
-            up = C.byref(ukf)
         elif u_out is not None:
             raise ValueError("u_out needs ukf (dt, wheel_radius, wheel_base)")
         self._last_u = u_out
-        _lib.check(_lib.load().lslam_scan_match(self.ctx.handle, C.byref(b), C.byref(self.p), up), "lslam_scan_match")
+        _lib.call("lslam_scan_match", self.ctx, b, self.p, ukf)
         if sync:
             self.ctx.sync()
 
@@ -174,31 +135,19 @@ class LidarOdometry:
         wheel radius and wheel base), where ``lm.step(...)`` without ``u`` finds them.  Given device
         points and ``sync=False`` a step waits for the host only where a longer revolution grows a copy."""
         ctx, R = self.ctx, self.R
-        if isinstance(xy, MapInput):
-            xy, scan_chunk_off, chunk_pt_off = xy.xy, xy.sco, xy.cpo
-        sco = np.ascontiguousarray(scan_chunk_off, np.int64).reshape(-1)
-        cpo = np.ascontiguousarray(chunk_pt_off, np.int64).reshape(-1)
-        if sco.size != R + 1:
-            raise ValueError("one revolution per robot: scan_chunk_off needs n_robots + 1 entries")
-        off = cpo[sco]
-        p0, p1 = int(off[0]), int(off[-1])
-        n = p1 - p0
-        if p0 < 0 or np.any(np.diff(off) < 0):
-            raise ValueError("inconsistent CSR offsets")
+        xy, off = staging.point_offsets(xy, scan_chunk_off, chunk_pt_off, R)
+        p0 = int(off[0])
+        n = int(off[-1]) - p0
         # the caller's device array may be an express ring that the next step overwrites: copy
         cur = self._xy[1].reserve(2 * n)
         if self.steps == 0:
             self._xy[0].reserve(2 * n)  # both copies are sized by the first step: the second one's grow would sync
         if isinstance(xy, DeviceArray):
-            if xy.dtype != np.float64 or xy.nbytes < 16 * p1:
-                raise ValueError("device xy must be float64 [n, 2] with n >= the last point offset")
+            staging.check_device_points(xy, off)
             if n:
                 ctx.copy(cur, xy.addr + 16 * p0, 16 * n)
         else:
-            h = np.ascontiguousarray(xy, np.float64).reshape(-1, 2)
-            if h.shape[0] < p1:
-                raise ValueError("xy holds fewer points than chunk_pt_off describes")
-            self._xy[1].put_host(h[p0:p1])
+            self._xy[1].put_host(staging.points_on_host(xy, off))
         # on the stream, behind the match that read this buffer two steps ago (ctx._inflight holds the array)
         self._off[1].upload_async(np.ascontiguousarray(off - p0, np.int32))
         self._n[1] = n

@@ -306,7 +306,7 @@ def test_refusals(ctx):
     f.fuse(xy, sco, cpo, x=x, P=P)  # fills a whole batch; then z on the mean is refused and nothing is written
     before = x.download()
     o, fo = f._align, f._fuse
-    b.a.xy, b.a.pt_off, b.a.pose, b.a.origin, b.a.d2 = f._xy.buf.addr, f._off.addr, x.addr, g.origin.addr, f.d2.addr
+    b.a.xy, b.a.pt_off, b.a.pose, b.a.origin, b.a.d2 = f._stage.xy.buf.addr, f._stage.off.addr, x.addr, g.origin.addr, f.d2.addr
     b.a.pose_out, b.a.trace, b.a.normal = x.addr, o["trace"].addr, o["normal"].addr
     b.a.n_used, b.a.iters, b.a.flags = o["n_used"].addr, o["iters"].addr, o["flags"].addr
     b.P, b.P_out, b.z = P.addr, P.addr, x.addr + 24
