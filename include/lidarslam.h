@@ -522,6 +522,28 @@ typedef struct lslam_recentre_batch {
     int32_t *flags;           /* [n_robots] LSLAM_RECENTRE_* */
 } lslam_recentre_batch;
 
+/* ---- page flags (lslam_page_batch.flags) ---- */
+enum {
+    LSLAM_PAGE_LOST = 1       /* cells that left the window were off the canvas: they are gone */
+};
+
+/* The paged rolling grid (lslam_grid_recentre_paged, lslam_grid_page_flush, lslam_grid_page_load), 16 bytes. */
+typedef struct lslam_page_params {
+    int32_t canvas_w;         /* cells a side of every robot's canvas; 16..2048 (2048) */
+    int32_t reserved[3];
+} lslam_page_params;
+
+/* One canvas per robot, 40 bytes; all pointers DEVICE memory.  flags is required by
+ * lslam_grid_recentre_paged alone: flush and load neither read nor write it. */
+typedef struct lslam_page_batch {
+    int32_t n_robots;
+    int32_t reserved;
+    int16_t *canvas;          /* [n_robots][canvas_w][canvas_w] in/out, row Y */
+    int32_t *win;             /* [n_robots][2] in/out (wx, wy): the canvas coordinates of window cell (0, 0) */
+    int32_t *moved;           /* [n_robots][2] (cells stored to the canvas, cells loaded from it) */
+    int32_t *flags;           /* [n_robots] LSLAM_PAGE_* */
+} lslam_page_batch;
+
 /* ---- distance-field modes (lslam_dist_params.mode) and flags (lslam_dist_batch.flags) ---- */
 enum {
     LSLAM_DIST_OCC = 0,       /* the sources are the occupied cells: L >= occ_min */
@@ -715,6 +737,8 @@ int lslam_fieldalign_abi_sizes(int64_t *sizes, int n);
 int lslam_fieldfuse_abi_sizes(int64_t *sizes, int n);
 /* and for lslam_relocprior_params, lslam_relocprior_batch.  Writes min(n, 2) entries, returns 2. */
 int lslam_relocprior_abi_sizes(int64_t *sizes, int n);
+/* and for lslam_page_params, lslam_page_batch.  Writes min(n, 2) entries, returns 2. */
+int lslam_page_abi_sizes(int64_t *sizes, int n);
 /* per-kernel HIP-event timing on the ctx stream (kernel ids: LSLAM_K_*) */
 enum { LSLAM_K_POLAR = 0, LSLAM_K_HYP = 1, LSLAM_K_PIPELINE = 2, LSLAM_K_LANDMARK = 3, LSLAM_K_UKF = 4,
        LSLAM_K_RNG = 5 /* parity-stream producer */, LSLAM_K_CONSENSUS = 6 /* per-chunk A4-A8 */,
@@ -757,6 +781,7 @@ int lslam_fieldscore_params_default(lslam_fieldscore_params *p);
 int lslam_fieldalign_params_default(lslam_fieldalign_params *p);
 int lslam_fieldfuse_params_default(lslam_fieldfuse_params *p);
 int lslam_relocprior_params_default(lslam_relocprior_params *p);
+int lslam_page_params_default(lslam_page_params *p);
 /* smallest e with RN(sqrt(e)) >= thr: (residual < thr) <=> (squared residual < cutoff) */
 double lslam_inlier_cutoff(double thr);
 /* MerweScaledSigmaPoints weights (filterpy _compute_weights) for n = 3 */
@@ -1070,6 +1095,57 @@ int lslam_grid_raycast(lslam_ctx *ctx, const lslam_raycast_batch *b, const lslam
  * checked before the context is touched; n_robots == 0 does nothing. */
 int lslam_grid_recentre(lslam_ctx *ctx, const lslam_recentre_batch *b, const lslam_grid_params *g,
                         const lslam_recentre_params *p);
+
+/* The paged rolling grid: a world canvas behind each robot's window.  lslam_grid_recentre loses what
+ * scrolls off; with a canvas the strip that leaves is written there and the strip that enters is read
+ * from there, so a robot that comes back finds its room.  New per-robot state, in device memory:
+ *   canvas[n_robots][Cw][Cw] int16, row Y, Cw = canvas_w (pp, 16..2048);
+ *   win[n_robots][2] int32 in/out, (wx, wy): the canvas coordinates of window cell (0, 0).  It may be
+ *   negative or beyond the canvas: the window may hang off the canvas partly or wholly.
+ * Window cell (x, y) is ON THE CANVAS iff 0 <= wx + x < Cw and 0 <= wy + y < Cw, tested in 64-bit
+ * arithmetic (win itself is 32 bits; win + shift is stored as its low 32 bits).
+ *
+ * lslam_grid_recentre_paged: recentre batch b, page batch pg (the same n_robots), g, p as
+ * lslam_grid_recentre takes them, and pp.  W = grid_w, L = logodds.  Per robot r:
+ *   1. steps 0 to 3 of lslam_grid_recentre exactly as written there: robot cell, bad pose, shift
+ *      (sx, sy), new origin with its non-finite case.  A bad pose or a shift of (0, 0) changes nothing
+ *      in logodds, origin, canvas or win; moved[r] = (0, 0) and pg.flags[r] = 0, and b's shift[r] and
+ *      flags[r] are what lslam_grid_recentre writes.
+ *   2. store.  Every window cell (x, y) whose destination (x - sx, y - sy) is off the window leaves
+ *      it.  On the canvas: canvas[wy + y][wx + x] = L[y][x], the 16-bit pattern.  Off the canvas: it
+ *      is dropped, and pg.flags[r] |= LSLAM_PAGE_LOST.
+ *   3. shift.  L'[y][x] = L[y + sy][x + sx] where that source is on the window (step 4 of
+ *      lslam_grid_recentre).  Every other cell (x, y) ENTERS: it takes
+ *      canvas[wy + sy + y][wx + sx + x] if that cell is on the canvas, 0 otherwise.
+ *   4. win[r] = win[r] + (sx, sy); moved[r] = (cells stored in step 2, cells loaded from the canvas in
+ *      step 3); b's shift[r], flags[r] (MOVED, CLEARED) and origin[r] as lslam_grid_recentre writes
+ *      them.  With |sx| >= W or |sy| >= W every cell leaves and every cell enters.
+ * Invariant.  The WORLD VIEW V is the canvas with the window laid over it: V[cy][cx] = L[cy - wy][cx - wx]
+ * where that is a window cell, canvas[cy][cx] elsewhere.  This call leaves V unchanged at every canvas
+ * cell: a cell that leaves takes its value to the place where V showed it, a cell that enters brings
+ * the value V showed.
+ *
+ * lslam_grid_page_flush: canvas[wy + y][wx + x] = logodds[y][x] for every window cell on the canvas;
+ * after it the canvas IS the world view.  The window and win are read only; moved[r] = (cells stored, 0).
+ * lslam_grid_page_load, the reverse: logodds[y][x] = canvas[wy + y][wx + x] where (x, y) is on the canvas,
+ * 0 elsewhere; the canvas and win are read only; moved[r] = (0, cells loaded).  It starts a robot in a
+ * stored map.  Neither touches pg.flags (it may be NULL for them).
+ *
+ * The canvas as a grid: a reader given canvas as logodds, canvas_w as grid_w and the origin
+ * origin - win cell sees the world view (after a flush).  That origin is constant while origin moves
+ * by multiples of cell that FP64 holds exactly: the caveat of step 3 of lslam_grid_recentre.
+ * The canvas costs 2 Cw Cw bytes a robot: 8 MiB at 2048, 32 GiB for 4096 robots.  It does not grow;
+ * what leaves it is lost.
+ * canvas must not overlap logodds (LSLAM_ERR_ARG).  All three run on the context's main stream, after
+ * every earlier call and before every later one, with no host synchronisation inside.  Out-of-range
+ * parameters and missing pointers return LSLAM_ERR_ARG (the message names the field), checked before
+ * the context is touched; n_robots == 0 does nothing. */
+int lslam_grid_recentre_paged(lslam_ctx *ctx, const lslam_recentre_batch *b, const lslam_page_batch *pg,
+                              const lslam_grid_params *g, const lslam_recentre_params *p, const lslam_page_params *pp);
+int lslam_grid_page_flush(lslam_ctx *ctx, const lslam_page_batch *pg, const int16_t *logodds, const lslam_grid_params *g,
+                          const lslam_page_params *pp);
+int lslam_grid_page_load(lslam_ctx *ctx, const lslam_page_batch *pg, int16_t *logodds, const lslam_grid_params *g,
+                         const lslam_page_params *pp);
 
 /* Distance field: for every cell of every robot's grid, the squared Euclidean distance, in cells, to
  * the nearest source cell, saturated: the clearance of a planner, the likelihood field of a scorer.

@@ -40,6 +40,7 @@ RAYCAST_BAD_POSE = 1
 RAYCAST_INVALID, RAYCAST_MATCH, RAYCAST_NOVEL, RAYCAST_THROUGH, RAYCAST_UNMAPPED = 0, 1, 2, 3, 4  # cls & 15
 RAYCAST_KIND_NONE, RAYCAST_KIND_UNKNOWN, RAYCAST_KIND_OCC = 0, 1, 2  # cls >> 4
 RECENTRE_BAD_POSE, RECENTRE_MOVED, RECENTRE_CLEARED = 1, 2, 4
+PAGE_LOST = 1
 DIST_OCC, DIST_NOT_FREE = 0, 1  # lslam_dist_params.mode
 DIST_EMPTY = 1
 FIELD_BAD_POSE = 1
@@ -176,6 +177,14 @@ class RecentreBatch(C.Structure):
                [(n, _VP) for n in ("pose", "origin", "logodds", "shift", "flags")]
 
 
+class PageParams(C.Structure):
+    _fields_ = [("canvas_w", C.c_int32), ("reserved", C.c_int32 * 3)]
+
+
+class PageBatch(C.Structure):
+    _fields_ = [("n_robots", C.c_int32), ("reserved", C.c_int32)] + [(n, _VP) for n in ("canvas", "win", "moved", "flags")]
+
+
 class DistParams(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("mode", "occ_min", "free_max", "d_max")]
 
@@ -237,6 +246,8 @@ EXPORTS = [
     "lslam_fieldalign_abi_sizes", "lslam_fieldalign_params_default", "lslam_field_align",
     "lslam_fieldfuse_abi_sizes", "lslam_fieldfuse_params_default", "lslam_field_fuse",
     "lslam_relocprior_abi_sizes", "lslam_relocprior_params_default", "lslam_map_relocalize_prior",
+    "lslam_page_abi_sizes", "lslam_page_params_default", "lslam_grid_recentre_paged", "lslam_grid_page_flush",
+    "lslam_grid_page_load",
 ]
 
 _lib = None
@@ -336,6 +347,12 @@ def load():
         "lslam_relocprior_params_default": ([P(RelocPriorParams)], C.c_int),
         "lslam_map_relocalize_prior": ([_VP, P(RelocPriorBatch), P(GridParams), P(MapMatchParams), P(RelocParams),
                                         P(RelocPriorParams)], C.c_int),
+        "lslam_page_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_page_params_default": ([P(PageParams)], C.c_int),
+        "lslam_grid_recentre_paged": ([_VP, P(RecentreBatch), P(PageBatch), P(GridParams), P(RecentreParams), P(PageParams)],
+                                      C.c_int),
+        "lslam_grid_page_flush": ([_VP, P(PageBatch), _VP, P(GridParams), P(PageParams)], C.c_int),
+        "lslam_grid_page_load": ([_VP, P(PageBatch), _VP, P(GridParams), P(PageParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -387,6 +404,7 @@ _ABI_SIZES = [
     ("lslam_fieldalign_abi_sizes", (FieldAlignParams, FieldAlignBatch)),
     ("lslam_fieldfuse_abi_sizes", (FieldFuseParams, FieldFuseBatch)),
     ("lslam_relocprior_abi_sizes", (RelocPriorParams, RelocPriorBatch)),
+    ("lslam_page_abi_sizes", (PageParams, PageBatch)),
 ]
 
 
@@ -449,6 +467,7 @@ fieldscore_params = _params_factory("fieldscore", FieldScoreParams)
 fieldalign_params = _params_factory("fieldalign", FieldAlignParams)
 fieldfuse_params = _params_factory("fieldfuse", FieldFuseParams)
 relocprior_params = _params_factory("relocprior", RelocPriorParams)
+page_params = _params_factory("page", PageParams)
 
 
 def ukf_params(n_landmarks, **kw):

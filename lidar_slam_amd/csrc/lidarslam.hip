@@ -16,7 +16,8 @@
 //   lslam_fieldalign.h (the Gauss-Newton alignment in the field; a point's terms and the 3 x 3 solve
 //   are lslam_fieldalign_core.h, plain C++), lslam_fieldfuse.h (the alignment fused into the filter; its
 //   3 x 3 algebra is lslam_fieldfuse_core.h, plain C++), lslam_relocprior.h (relocalisation over an
-//   admissible set: the free-space prior and the search window);
+//   admissible set: the free-space prior and the search window), lslam_page.h (the paged rolling
+//   grid: a canvas behind each window; its strips and their clipping are lslam_page_plan.h, plain C++);
 // the host side is included at the foot:
 //   lslam_hazards.h  which waits a call's producer needs (plain C++, no HIP)
 //   lslam_ctx.h      lslam_ctx, its grow-only device buffers and timers, create / destroy,
@@ -3080,6 +3081,8 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
 #include "lslam_fieldfuse.h"
 // the relocalisation priors' three kernels, templates too: the newest, so the code object's last
 #include "lslam_relocprior.h"
+// the paged rolling grid's kernels, templates built on the recentre kernel's device functions: the newest
+#include "lslam_page.h"
 
 // ------------------------------------------------------------------------
 // host side: the context, then the launchers and entry points

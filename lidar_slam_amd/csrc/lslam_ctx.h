@@ -434,6 +434,12 @@ int lslam_relocprior_abi_sizes(int64_t *sizes, int n) {
     return 2;
 }
 
+int lslam_page_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[2] = {(int64_t)sizeof(lslam_page_params), (int64_t)sizeof(lslam_page_batch)};
+    for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
+    return 2;
+}
+
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
     if (!c || (!dst && n)) return LSLAM_ERR_ARG;
     if (!n) return LSLAM_OK;
@@ -672,6 +678,13 @@ int lslam_relocprior_params_default(lslam_relocprior_params *p) {
     p->half_xy = 1000.0;   // mm: a filter that has drifted a metre ...
     p->half_theta = 0.5;   // ... and twenty-odd degrees still has its pose inside the window
     p->clear_min2 = 16;    // four fine cells: one coarse cell at the default factor
+    return LSLAM_OK;
+}
+
+int lslam_page_params_default(lslam_page_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->canvas_w = 2048;  // cells: 40.96 m a side at 20 mm, sixteen default windows; 8 MiB a robot
     return LSLAM_OK;
 }
 

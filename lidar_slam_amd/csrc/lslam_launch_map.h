@@ -652,6 +652,100 @@ static int launch_recentre(lslam_ctx *c, const lslam_recentre_batch *b, const ls
                          {b->flags, R * 4}});
 }
 
+// ---- the paged rolling grid (lslam_page.h) ----
+
+static int page_check_params(const lslam_page_params *pp) {
+    if (!pp) return set_err(LSLAM_ERR_ARG, "page: params is NULL");
+    if (pp->canvas_w < 16 || pp->canvas_w > 2048) return set_err(LSLAM_ERR_ARG, "page: canvas_w must be in [16, 2048]");
+    return LSLAM_OK;
+}
+
+// the two batches of a paged recentre, and the window of a flush or a load with its page batch: what
+// the entry frame takes as one batch
+struct PagedBatch {
+    lslam_recentre_batch b;
+    lslam_page_batch pg;
+};
+struct PageWindowBatch {
+    lslam_page_batch pg;
+    const int16_t *logodds;
+    bool store;  // flush: the window is the input and the canvas the output
+};
+
+static Reqs paged_reqs(const PagedBatch &x) {
+    const Reqs pg = {{{"win", x.pg.win}, {"canvas", x.pg.canvas}}, {{"moved", x.pg.moved}, {"page flags", x.pg.flags}}, x.pg.n_robots};
+    Reqs r = reqs_join(recentre_reqs(x.b), pg);
+    // (one size rules both: a negative one of either is reported, and an empty call is empty in both)
+    r.n = x.b.n_robots < 0 || x.pg.n_robots < 0 ? -1 : std::max(x.b.n_robots, x.pg.n_robots);
+    return r;
+}
+
+static Reqs page_window_reqs(const PageWindowBatch &x) {
+    if (x.store) return {{{"logodds", x.logodds}, {"win", x.pg.win}}, {{"canvas", x.pg.canvas}, {"moved", x.pg.moved}}, x.pg.n_robots};
+    return {{{"canvas", x.pg.canvas}, {"win", x.pg.win}}, {{"logodds", x.logodds}, {"moved", x.pg.moved}}, x.pg.n_robots};
+}
+
+static int page_check_overlap(const lslam_page_batch &pg, const void *logodds, const lslam_grid_params *g, const lslam_page_params *pp) {
+    const size_t R = (size_t)pg.n_robots;
+    if (ranges_overlap(logodds, R * (size_t)g->grid_w * (size_t)g->grid_w * 2, pg.canvas, R * (size_t)pp->canvas_w * (size_t)pp->canvas_w * 2))
+        return set_err(LSLAM_ERR_ARG, "page: canvas overlaps logodds");
+    return LSLAM_OK;
+}
+
+// One workgroup per robot, as launch_recentre and under its timing slot: the call is a whole recentre.
+static int launch_recentre_paged(lslam_ctx *c, const PagedBatch &x, const lslam_grid_params *g, const lslam_recentre_params *p,
+                                 const lslam_page_params *pp) {
+    PageArgs k;
+    memset(&k, 0, sizeof(k));
+    k.pose = x.b.pose, k.origin = x.b.origin, k.logodds = x.b.logodds, k.shift = x.b.shift, k.flags = x.b.flags;
+    k.canvas = x.pg.canvas, k.win = x.pg.win, k.moved = x.pg.moved, k.pflags = x.pg.flags;
+    k.cell = g->cell;
+    k.inv = 1.0 / g->cell;
+    k.n_robots = x.b.n_robots;
+    k.grid_w = g->grid_w;
+    k.margin = p->margin;
+    k.quantum = p->quantum;
+    k.band_rows = recentre_band_rows(g->grid_w);
+    k.vec = groups16(g->grid_w, x.b.logodds);
+    k.canvas_w = pp->canvas_w;
+    k.pvec = k.vec && groups16(pp->canvas_w, x.pg.canvas);
+    if (x.b.n_robots > (1 << 30)) return map_err(LSLAM_ERR_UNSUPPORTED, "page", "too many robots in one call");
+    int st = timer_begin(c, LSLAM_K_RECENTRE);
+    if (st) return st;
+    const dim3 blocks((unsigned)recentre_blocks(x.b.n_robots));
+    if (k.vec && p->quantum % 8 == 0) hipLaunchKernelGGL(page_recentre_kernel<0>, blocks, dim3(PAGE_TPB), 0, c->stream, k);
+    else hipLaunchKernelGGL(page_recentre_kernel<1>, blocks, dim3(PAGE_TPB), 0, c->stream, k);
+    HIPCHK(hipGetLastError());
+    if ((st = timer_end(c, LSLAM_K_RECENTRE))) return st;
+    const size_t R = (size_t)x.b.n_robots, W = (size_t)g->grid_w, Cw = (size_t)pp->canvas_w;
+    return note_outs(c, {{x.b.logodds, R * W * W * 2}, {x.b.origin, R * 16}, {x.b.shift, R * 8}, {x.b.flags, R * 4},
+                         {x.pg.canvas, R * Cw * Cw * 2}, {x.pg.win, R * 8}, {x.pg.moved, R * 8}, {x.pg.flags, R * 4}});
+}
+
+// A robot's rows in slices (slices_for), each of whole rows.
+static int launch_page_window(lslam_ctx *c, const PageWindowBatch &x, const lslam_grid_params *g, const lslam_page_params *pp) {
+    PageWindowArgs k;
+    memset(&k, 0, sizeof(k));
+    k.pg = x.pg;
+    k.logodds = const_cast<int16_t *>(x.logodds);
+    k.grid_w = g->grid_w;
+    k.canvas_w = pp->canvas_w;
+    k.vec = groups16(g->grid_w, x.logodds) && groups16(pp->canvas_w, x.pg.canvas);
+    const int64_t n = x.pg.n_robots;
+    const int want = (int)slices_for(c, n, g->grid_w);
+    k.rows = (g->grid_w + want - 1) / want;
+    k.n_slices = (g->grid_w + k.rows - 1) / k.rows;
+    int st = check_blocks("page", n * k.n_slices);
+    if (st) return st;
+    const dim3 blocks((unsigned)(n * k.n_slices));
+    if (x.store) hipLaunchKernelGGL(page_window_kernel<true>, blocks, dim3(PAGE_TPB), 0, c->stream, k);
+    else hipLaunchKernelGGL(page_window_kernel<false>, blocks, dim3(PAGE_TPB), 0, c->stream, k);
+    HIPCHK(hipGetLastError());
+    const size_t R = (size_t)n, W = (size_t)g->grid_w, Cw = (size_t)pp->canvas_w;
+    if (x.store) return note_outs(c, {{x.pg.canvas, R * Cw * Cw * 2}, {x.pg.moved, R * 8}});
+    return note_outs(c, {{x.logodds, R * W * W * 2}, {x.pg.moved, R * 8}});
+}
+
 // ---- distance field and its read (lslam_dist.h) ----
 
 static int dist_check_params(const lslam_dist_params *p) {
@@ -1033,6 +1127,44 @@ int lslam_grid_recentre(lslam_ctx *c, const lslam_recentre_batch *b, const lslam
     int st = grid_check_params(g);
     if (st || (st = recentre_check_params(p, g))) return st;
     return map_entry("recentre", c, b, recentre_reqs, [&] { return launch_recentre(c, b, g, p); });
+}
+
+// On the main stream, as lslam_grid_recentre.
+int lslam_grid_recentre_paged(lslam_ctx *c, const lslam_recentre_batch *b, const lslam_page_batch *pg, const lslam_grid_params *g,
+                              const lslam_recentre_params *p, const lslam_page_params *pp) {
+    int st = grid_check_params(g);
+    if (st || (st = recentre_check_params(p, g)) || (st = page_check_params(pp))) return st;
+    PagedBatch x;
+    if (b && pg) x = {*b, *pg};
+    return map_entry(
+        "page", c, b && pg ? &x : nullptr, paged_reqs,
+        [&]() -> int {
+            if (b->n_robots != pg->n_robots) return set_err(LSLAM_ERR_ARG, "page: n_robots of the two batches differ");
+            return page_check_overlap(*pg, b->logodds, g, pp);
+        },
+        [&] { return launch_recentre_paged(c, x, g, p, pp); });
+}
+
+// On the main stream: a flush after the calls that wrote the window, a load before the calls that read it.
+static int page_window_entry(lslam_ctx *c, const lslam_page_batch *pg, const int16_t *logodds, bool store,
+                             const lslam_grid_params *g, const lslam_page_params *pp) {
+    int st = grid_check_params(g);
+    if (st || (st = page_check_params(pp))) return st;
+    PageWindowBatch x;
+    if (pg) x = {*pg, logodds, store};
+    return map_entry(
+        "page", c, pg ? &x : nullptr, page_window_reqs, [&] { return page_check_overlap(*pg, logodds, g, pp); },
+        [&] { return launch_page_window(c, x, g, pp); });
+}
+
+int lslam_grid_page_flush(lslam_ctx *c, const lslam_page_batch *pg, const int16_t *logodds, const lslam_grid_params *g,
+                          const lslam_page_params *pp) {
+    return page_window_entry(c, pg, logodds, true, g, pp);
+}
+
+int lslam_grid_page_load(lslam_ctx *c, const lslam_page_batch *pg, int16_t *logodds, const lslam_grid_params *g,
+                         const lslam_page_params *pp) {
+    return page_window_entry(c, pg, logodds, false, g, pp);
 }
 
 // On the main stream, as lslam_grid_raycast: after the calls that wrote the grid.

@@ -51,13 +51,15 @@ struct RecentreArgs {
 __host__ __device__ static inline int recentre_robot_of_block(int b) { return b ^ (((b >> 3) ^ (b >> 6)) & 7); }
 static inline int recentre_blocks(int n_robots) { return (n_robots + 7) & ~7; }
 
-template <int CELLS>
-__global__ __launch_bounds__(RECENTRE_TPB) void recentre_kernel(const RecentreArgs a) {
-    const int tid = (int)threadIdx.x, r = recentre_robot_of_block((int)blockIdx.x);
-    const int W = a.grid_w;
-    if (r >= a.b.n_robots) return;  // (the grid is padded to whole groups of 8 blocks)
+// Steps 0 to 3 of the definition for robot r: the one text of the decision, for this kernel and for
+// the paged one (lslam_page.h).  Every thread computes it with the same instructions.
+struct RecentreDecision {
+    int sx, sy, flag;
+    double nox, noy;  // the new origin (the old one where nothing moves)
+};
 
-    // ---- 0. the decision: steps 0 to 3 ----
+__device__ __forceinline__ RecentreDecision recentre_decide(const RecentreArgs &a, int r) {
+    const int W = a.grid_w;
     const double px = a.b.pose[3 * r], py = a.b.pose[3 * r + 1], th = a.b.pose[3 * r + 2];
     const double ox = a.b.origin[2 * r], oy = a.b.origin[2 * r + 1];
     const double X0d = floor((px - ox) * a.inv), Y0d = floor((py - oy) * a.inv);
@@ -84,16 +86,15 @@ __global__ __launch_bounds__(RECENTRE_TPB) void recentre_kernel(const RecentreAr
             }
         }
     }
-    if (tid == 0) {
-        a.b.shift[2 * r] = sx;
-        a.b.shift[2 * r + 1] = sy;
-        a.b.flags[r] = flag;
-    }
-    if (!(sx | sy)) return;  // (uniform: every thread holds the same decision)
+    return {sx, sy, flag, nox, noy};
+}
 
-    // ---- 1. the grid, band after band ----
+// Step 4 for one robot's grid L, by the whole workgroup: the bands of the plan, in its order.  Every
+// band's stores stand behind a workgroup barrier that follows the band's loads.
+template <int CELLS>
+__device__ __forceinline__ void recentre_move(const RecentreArgs &a, int16_t *L, int sx, int sy, int tid) {
+    const int W = a.grid_w;
     const RecentrePlan p = recentre_plan(W, sx, sy, a.band_rows);
-    int16_t *L = a.b.logodds + (int64_t)r * W * W;
     bool groups = true;
     if constexpr (CELLS != 0) groups = a.vec && (sx & 7) == 0;
     if (groups) {
@@ -138,11 +139,29 @@ __global__ __launch_bounds__(RECENTRE_TPB) void recentre_kernel(const RecentreAr
             for (int i = tid; i < n; i += RECENTRE_TPB) L1[b.y0 * W + i] = buf[i];
         }
     }
+}
+
+template <int CELLS>
+__global__ __launch_bounds__(RECENTRE_TPB) void recentre_kernel(const RecentreArgs a) {
+    const int tid = (int)threadIdx.x, r = recentre_robot_of_block((int)blockIdx.x);
+    if (r >= a.b.n_robots) return;  // (the grid is padded to whole groups of 8 blocks)
+
+    // ---- 0. the decision: steps 0 to 3 ----
+    const RecentreDecision d = recentre_decide(a, r);
+    if (tid == 0) {
+        a.b.shift[2 * r] = d.sx;
+        a.b.shift[2 * r + 1] = d.sy;
+        a.b.flags[r] = d.flag;
+    }
+    if (!(d.sx | d.sy)) return;  // (uniform: every thread holds the same decision)
+
+    // ---- 1. the grid, band after band ----
+    recentre_move<CELLS>(a, a.b.logodds + (int64_t)r * a.grid_w * a.grid_w, d.sx, d.sy, tid);
 
     // ---- 2. the origin: every thread read it before the barriers above ----
     if (tid == 0) {
-        a.b.origin[2 * r] = nox;
-        a.b.origin[2 * r + 1] = noy;
+        a.b.origin[2 * r] = d.nox;
+        a.b.origin[2 * r + 1] = d.noy;
     }
 }
 

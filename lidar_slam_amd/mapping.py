@@ -28,6 +28,7 @@ from .staging import Staging, _Grow
 
 GRID_BAD_POSE, GRID_CLIPPED = _lib.GRID_BAD_POSE, _lib.GRID_CLIPPED
 RECENTRE_BAD_POSE, RECENTRE_MOVED, RECENTRE_CLEARED = _lib.RECENTRE_BAD_POSE, _lib.RECENTRE_MOVED, _lib.RECENTRE_CLEARED
+PAGE_LOST = _lib.PAGE_LOST
 DIST_OCC, DIST_NOT_FREE, DIST_EMPTY, FIELD_BAD_POSE = _lib.DIST_OCC, _lib.DIST_NOT_FREE, _lib.DIST_EMPTY, _lib.FIELD_BAD_POSE
 FIELDALIGN_BAD_POSE, FIELDALIGN_CONVERGED, FIELDALIGN_SINGULAR = _lib.FIELDALIGN_BAD_POSE, _lib.FIELDALIGN_CONVERGED, _lib.FIELDALIGN_SINGULAR
 FIELDALIGN_FEW, FIELDALIGN_DIVERGED, FIELDALIGN_WEAK = _lib.FIELDALIGN_FEW, _lib.FIELDALIGN_DIVERGED, _lib.FIELDALIGN_WEAK
@@ -53,14 +54,29 @@ class OccupancyGrid:
     (``lslam_grid_params``; defaults 20 mm, 8000 mm, 512, 85, -41, -200, 350; log-odds in 0.01 nat).
     ``origin`` [R, 2] (or one pair for all): the world coordinates of the corner of cell (0, 0);
     default: every grid centred on (0, 0).  ``recentre`` moves it, on the device; ``origin_host`` is
-    the host's copy, refreshed on its next read after a ``recentre``."""
+    the host's copy, refreshed on its next read after a ``recentre``.
 
-    def __init__(self, ctx: Context, n_robots: int, origin=None, **params):
+    ``canvas_w``: a world canvas of ``canvas_w`` x ``canvas_w`` cells behind every robot's grid (16..2048;
+    ``lslam_page_params``), which is then a window onto it: ``recentre`` writes the strip that leaves
+    the window to the canvas and reads the strip that enters from it (``lslam_grid_recentre_paged``), so
+    a robot that comes back finds the room it mapped.  Without it nothing is allocated and ``recentre``
+    loses what scrolls off.  The canvas costs 2 canvas_w^2 bytes a robot: 8 MiB at 2048, 32 GiB for
+    4096 robots; it does not grow, and what leaves it is lost (``PAGE_LOST``).  ``win`` [R, 2] (or one
+    pair): the canvas coordinates of window cell (0, 0); default: the window in the middle of the
+    canvas, rounded down to a multiple of 8 (the 16-byte path needs it so).  ``canvas_origin``, on the
+    device and set once here, is origin - win * cell: the world corner of canvas cell (0, 0).  It stays
+    the canvas' origin exactly while the origins are multiples of ``cell`` that FP64 holds exactly (the
+    caveat of ``lslam_grid_recentre``'s two roundings)."""
+
+    def __init__(self, ctx: Context, n_robots: int, origin=None, canvas_w=None, win=None, _view=None, **params):
         R = int(n_robots)
         if R <= 0:
             raise ValueError("n_robots must be > 0")
         self.ctx, self.R = ctx, R
-        self.p = _lib.grid_params(**params)
+        if canvas_w is None and win is not None:
+            raise ValueError("win needs canvas_w")
+        # (_view, world()'s: the params, origin and logodds of existing device buffers instead of new ones)
+        self.p = _view[0] if _view else _lib.grid_params(**params)
         self.W = int(self.p.grid_w)
         half = 0.5 * self.W * self.p.cell
         o = np.full((R, 2), -half) if origin is None else np.asarray(origin, np.float64)
@@ -68,9 +84,13 @@ class OccupancyGrid:
         self._origin_stale = False  # a recentre may have moved the device's origin since the last read
         # (a range error of params surfaces here, from the first call, before anything large is allocated)
         _lib.call("lslam_grid_update", ctx, _lib.GridBatch(), self.p)
-        self.origin = ctx.to_device(self._origin_host)
-        self.logodds = ctx.empty((R, self.W, self.W), np.int16)
-        self.logodds.fill_zero()
+        if _view:
+            self.origin, self.logodds = _view[1], _view[2]
+            self._origin_stale = True  # (the first read downloads it)
+        else:
+            self.origin = ctx.to_device(self._origin_host)
+            self.logodds = ctx.empty((R, self.W, self.W), np.int16)
+            self.logodds.fill_zero()
         self.rot = ctx.empty((R, 2), np.float64)
         self.n_used = ctx.empty((R, 2), np.int32)
         self.flags = ctx.empty(R, np.int32)
@@ -79,6 +99,39 @@ class OccupancyGrid:
         self._stage = Staging(ctx, R)
         self.steps = 0
         self._shift = self._rflags = None  # recentre's outputs, allocated by its first call
+        self.canvas_w = self.canvas = None
+        if canvas_w is not None:
+            self._init_canvas(int(canvas_w), win)
+
+    def _init_canvas(self, Cw, win):
+        ctx, R = self.ctx, self.R
+        if not 16 <= Cw <= 2048:  # (lslam_page_params.canvas_w's range, before the canvas is allocated)
+            raise ValueError("canvas_w must be in [16, 2048]")
+        self.pp = _lib.page_params(canvas_w=Cw)
+        mid = (Cw - self.W) // 2 // 8 * 8
+        w = np.full((R, 2), mid) if win is None else np.asarray(win)
+        if not np.issubdtype(w.dtype, np.integer):
+            raise ValueError("win must be integers")
+        if w.size and (w.min() < -2 ** 31 or w.max() >= 2 ** 31):
+            raise ValueError("win must fit 32 bits")
+        w = np.ascontiguousarray(np.broadcast_to(w, (R, 2)), np.int32)
+        self.canvas_w = Cw
+        self.canvas = ctx.empty((R, Cw, Cw), np.int16)
+        self.canvas.fill_zero()
+        self.win = ctx.to_device(w)
+        self.moved = ctx.empty((R, 2), np.int32)
+        self.page_flags = ctx.empty(R, np.int32)
+        for a in (self.moved, self.page_flags):
+            a.fill_zero()
+        self.canvas_origin = ctx.to_device(self._origin_host - w.astype(np.float64) * float(self.p.cell))
+
+    def _page_batch(self):
+        if self.canvas is None:
+            raise ValueError("this grid has no canvas (canvas_w)")
+        pg = _lib.PageBatch()
+        pg.n_robots = self.R
+        pg.canvas, pg.win, pg.moved, pg.flags = self.canvas.addr, self.win.addr, self.moved.addr, self.page_flags.addr
+        return pg
 
     @property
     def origin_host(self):
@@ -118,10 +171,12 @@ class OccupancyGrid:
     def recentre(self, pose, margin=None, quantum=None, sync=True):
         """Roll every grid whose robot is within ``margin`` cells of an edge (``lslam_grid_recentre``):
         the grid and ``origin`` move by whole cells, multiples of ``quantum``, in place on the device,
-        so that the robot's cell is back in the middle.  What scrolls off is lost; what scrolls in is
-        unknown.  ``pose`` as in ``step``; ``margin``, ``quantum``: ``lslam_recentre_params`` (defaults
-        128 and 8 cells).  The localizers and ray casters built on this grid read ``origin`` on the
-        device and follow."""
+        so that the robot's cell is back in the middle.  Without a canvas what scrolls off is lost and
+        what scrolls in is unknown; with one (``canvas_w``) the strip that leaves goes to the canvas and
+        the strip that enters comes from it (``lslam_grid_recentre_paged``), and only what leaves the
+        canvas is lost.  ``pose`` as in ``step``; ``margin``, ``quantum``: ``lslam_recentre_params``
+        (defaults 128 and 8 cells).  The localizers and ray casters built on this grid read ``origin`` on
+        the device and follow."""
         ctx, R = self.ctx, self.R
         kw = {k: int(v) for k, v in (("margin", margin), ("quantum", quantum)) if v is not None}
         q = _lib.recentre_params(**kw)
@@ -132,17 +187,51 @@ class OccupancyGrid:
         b.n_robots = R
         b.pose, b.origin, b.logodds = dpose.addr, self.origin.addr, self.logodds.addr
         b.shift, b.flags = self._shift.addr, self._rflags.addr
-        _lib.call("lslam_grid_recentre", ctx, b, self.p, q)
+        if self.canvas is None:
+            _lib.call("lslam_grid_recentre", ctx, b, self.p, q)
+        else:
+            _lib.call("lslam_grid_recentre_paged", ctx, b, self._page_batch(), self.p, q, self.pp)
         self._origin_stale = True
         if sync:
             ctx.sync()
 
     def recentre_results(self):
         """The last ``recentre``'s shift [R, 2] (sx, sy in cells), flags [R] (RECENTRE_*) and the origin
-        [R, 2] as it now stands."""
+        [R, 2] as it now stands; with a canvas also moved [R, 2] (cells stored to the canvas, cells loaded
+        from it), win [R, 2] as it now stands and page_flags [R] (``PAGE_LOST``)."""
         if self._shift is None:
             raise ValueError("no recentre yet")
-        return {"shift": self._shift.download(), "flags": self._rflags.download(), "origin": self.origin_host}
+        out = {"shift": self._shift.download(), "flags": self._rflags.download(), "origin": self.origin_host}
+        if self.canvas is not None:
+            out.update(moved=self.moved.download(), win=self.win.download(), page_flags=self.page_flags.download())
+        return out
+
+    def flush(self, sync=True):
+        """Write every window cell that is on the canvas to it (``lslam_grid_page_flush``): after it the
+        canvas is the world view.  ``moved`` becomes (cells stored, 0)."""
+        _lib.call("lslam_grid_page_flush", self.ctx, self._page_batch(), self.logodds.addr, self.p, self.pp)
+        if sync:
+            self.ctx.sync()
+
+    def load(self, sync=True):
+        """Fill the window from the canvas where it lies now, zero where it hangs off
+        (``lslam_grid_page_load``): the start of a robot in a stored map.  ``moved`` becomes
+        (0, cells loaded)."""
+        _lib.call("lslam_grid_page_load", self.ctx, self._page_batch(), self.logodds.addr, self.p, self.pp)
+        if sync:
+            self.ctx.sync()
+
+    def world(self, sync=True):
+        """The world view as a grid: ``flush``, then an ``OccupancyGrid``-shaped view of ``canvas_w`` cells a
+        side that SHARES the canvas buffer (``logodds`` is the canvas, ``origin`` is ``canvas_origin``).
+        ``GridRelocalizer``, ``GridLocalizer``, ``GridRayCaster`` and ``DistanceField`` take it as they take
+        a grid.  It is a view for reading: a ``step`` or ``recentre`` on it would write the canvas behind the
+        window's back.  Its origin agrees with the window's exactly when the origins are multiples of
+        ``cell`` that FP64 holds exactly."""
+        self.flush(sync=sync)
+        p = _lib.GridParams.from_buffer_copy(self.p)
+        p.grid_w = self.canvas_w
+        return OccupancyGrid(self.ctx, self.R, _view=(p, self.canvas_origin, self.canvas))
 
     def results(self):
         """logodds [R, W, W] int16 (row Y, 0.01 nat) and the last step's rot [R, 2], n_used [R, 2]
