@@ -1356,6 +1356,93 @@ int lslam_map_relocalize_prior(lslam_ctx *ctx, const lslam_relocprior_batch *b, 
                                const lslam_mapmatch_params *m, const lslam_reloc_params *q,
                                const lslam_relocprior_params *pp);
 
+/* ---- map merge (lslam_grid_merge): modes (lslam_gridmerge_params.mode) and flags (lslam_gridmerge_batch.flags) ---- */
+enum {
+    LSLAM_MERGE_ADD = 0,      /* the source's evidence is added: L' = clip(L + v) where v != 0 */
+    LSLAM_MERGE_FILL = 1      /* the source fills what the destination does not know: L' = clip(v) where L = 0 != v */
+};
+enum {
+    LSLAM_MERGE_MERGED = 1,    /* the destination took the source's evidence */
+    LSLAM_MERGE_WEAK = 2,      /* supported < min_support: too little common wall to judge the transform */
+    LSLAM_MERGE_CONFLICT = 4,  /* the contradicted share of the source's occupied cells is above max_contra_permille */
+    LSLAM_MERGE_SKIPPED = 8,   /* src_index outside 0..n_src-1: the pair does nothing */
+    LSLAM_MERGE_BAD_XFORM = 16 /* a component of xform or of an origin is not finite: the pair does nothing */
+};
+
+/* Map merge (lslam_grid_merge), 32 bytes.  The destination's geometry (grid_w, cell) and the clamps
+ * (l_min, l_max) come from the lslam_grid_params given with the call. */
+typedef struct lslam_gridmerge_params {
+    int32_t src_w;               /* cells a side of every source grid; 16..2048 (512).  It may differ from grid_w */
+    int32_t n_src;               /* source grids at src; >= 1 (1) */
+    int32_t occ_min;             /* a cell with L >= occ_min is occupied; -32768..32767 (85) */
+    int32_t mode;                /* LSLAM_MERGE_ADD (0) or LSLAM_MERGE_FILL */
+    int32_t dry_run;             /* 0 or 1: statistics and flags only (0) */
+    int32_t min_support;         /* gate: supported cells a merge needs; >= 0 (64) */
+    int32_t max_contra_permille; /* gate: most contradicted cells per 1000 supported or contradicted; 0..1000 (100) */
+    int32_t reserved;
+} lslam_gridmerge_params;
+
+/* One merge per pair, 72 bytes; all pointers DEVICE memory; all required but src_index. */
+typedef struct lslam_gridmerge_batch {
+    int32_t n_pairs;
+    int32_t reserved;
+    const int16_t *src;        /* [n_src][src_w][src_w], row Y: read only, must not overlap dst */
+    const double *src_origin;  /* [n_src][2] world coordinates (source frame) of the corner of source cell (0, 0) */
+    const int32_t *src_index;  /* [n_pairs], optional (NULL: pair m reads source m) */
+    int16_t *dst;              /* [n_pairs][grid_w][grid_w] in/out, row Y */
+    const double *dst_origin;  /* [n_pairs][2] */
+    const double *xform;       /* [n_pairs][4] (c, s, tx, ty): destination world -> source world */
+    int32_t *stats;            /* [n_pairs][8] */
+    int32_t *flags;            /* [n_pairs] LSLAM_MERGE_* */
+} lslam_gridmerge_batch;
+
+/* lslam_abi_sizes for lslam_gridmerge_params, lslam_gridmerge_batch.  Writes min(n, 2) entries, returns 2. */
+int lslam_gridmerge_abi_sizes(int64_t *sizes, int n);
+int lslam_gridmerge_params_default(lslam_gridmerge_params *p);
+
+/* Map merge: fold one map into another under a rigid transform, gated on their agreement.  Pair m reads
+ * source grid k = src_index[m] (m if src_index is NULL) and changes destination grid m.  The
+ * destination's geometry is g's grid_w and cell, W = grid_w, inv = 1.0 / cell; the source's is src_w
+ * (Sw) and the same cell.  xform[m] = (c, s, tx, ty) takes destination-world coordinates to
+ * source-world coordinates; its bits are the caller's (mapping.merge_transform in Python): there is no
+ * trigonometry in the library.  All FP64, every operation rounded on its own (nothing is fused), then
+ * integers.  Per pair m:
+ *   0. k outside 0..n_src-1: flags[m] = LSLAM_MERGE_SKIPPED, stats[m] all zero, nothing else happens.
+ *   1. if any of c, s, tx, ty, dst_origin[m] = (oxd, oyd), src_origin[k] = (oxs, oys) is not finite:
+ *      flags[m] = LSLAM_MERGE_BAD_XFORM, stats[m] all zero, nothing else happens.
+ *   2. the gather.  For destination cell (X, Y): wx = oxd + ((double)X + 0.5) cell, wy = oyd +
+ *      ((double)Y + 0.5) cell; xs = (c wx - s wy) + tx, ys = (s wx + c wy) + ty;
+ *      fx = floor((xs - oxs) inv), fy = floor((ys - oys) inv).  The cell is ON THE SOURCE MAP iff
+ *      0 <= fx < Sw and 0 <= fy < Sw, compared as doubles before any conversion (a NaN fails, so a
+ *      transform at 1e300 converts nothing).  v = src[k][fy][fx] there, 0 elsewhere: an inverse
+ *      nearest-neighbour gather, every destination cell decided exactly once, no holes under rotation.
+ *   3. classes, against the destination L as it stood before the call.  N(X, Y) iff some cell of the
+ *      3 x 3 block around (X, Y), clipped to the map, has L >= occ_min.  A cell with v >= occ_min is
+ *      SUPPORTED if N(X, Y); CONTRADICTED if not N(X, Y) and L[Y][X] < 0; NEW otherwise.
+ *      stats[m] = (cells on the source map, cells with v != 0, supported, contradicted, new, cells with
+ *      L != 0 != v of equal sign, cells with L != 0 != v of opposite sign, cells whose value changed).
+ *   4. gates.  LSLAM_MERGE_WEAK iff supported < min_support.  LSLAM_MERGE_CONFLICT iff
+ *      1000 contradicted > max_contra_permille (supported + contradicted), in 64 bits.  Either gate, or
+ *      dry_run, leaves dst bit for bit and the changed count 0; flags[m] = the gates that are set (0: a
+ *      dry run that would have merged).
+ *   5. otherwise flags[m] = LSLAM_MERGE_MERGED and, with l_min and l_max of g:
+ *      ADD:  where v != 0, L' = clip(L + v, l_min, l_max) (the sum in 32 bits);
+ *      FILL: where L = 0 and v != 0, L' = clip(v, l_min, l_max).
+ *      Every other cell keeps its bits, values outside [l_min, l_max] included.  The changed count is
+ *      the cells with L' != L.
+ * ADD counts evidence twice when the same source is merged twice; FILL does not.  The gates read
+ * occupied cells only: two maps without a common occupied cell merge WEAK.  The resampling is nearest
+ * neighbour: under rotation a one-cell wall may come out one cell off or doubled, which is what the
+ * one-cell tolerance of N is for.
+ * Two launches on the main stream (lslam_gridmerge.h): the statistics, then the merge, every workgroup
+ * of which takes the pair's decision from the finished counters; stats is the only scratch.  src must
+ * not overlap dst (LSLAM_ERR_ARG).  Runs on the context's main stream, after every earlier call, with
+ * no host synchronisation inside; there is no timing slot.  g is checked as lslam_grid_update checks
+ * it.  Out-of-range parameters and missing pointers return LSLAM_ERR_ARG (the message names the field),
+ * checked before the context is touched; n_pairs == 0 does nothing. */
+int lslam_grid_merge(lslam_ctx *ctx, const lslam_gridmerge_batch *b, const lslam_grid_params *g,
+                     const lslam_gridmerge_params *p);
+
 #ifdef __cplusplus
 }
 #endif

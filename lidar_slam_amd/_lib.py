@@ -47,6 +47,8 @@ FIELD_BAD_POSE = 1
 (FIELDALIGN_BAD_POSE, FIELDALIGN_CONVERGED, FIELDALIGN_SINGULAR, FIELDALIGN_FEW, FIELDALIGN_DIVERGED,
  FIELDALIGN_WEAK) = 1, 2, 4, 8, 16, 32
 FIELDFUSE_OUTLIER, FIELDFUSE_BAD_COV = 64, 128
+MERGE_ADD, MERGE_FILL = 0, 1  # lslam_gridmerge_params.mode
+MERGE_MERGED, MERGE_WEAK, MERGE_CONFLICT, MERGE_SKIPPED, MERGE_BAD_XFORM = 1, 2, 4, 8, 16
 
 
 class HIPLibraryError(RuntimeError):
@@ -222,6 +224,16 @@ class FieldFuseBatch(C.Structure):
     _fields_ = [("a", FieldAlignBatch)] + [(n, _VP) for n in ("P", "P_out", "z", "info", "info_f", "s2", "nis")]
 
 
+class GridMergeParams(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("src_w", "n_src", "occ_min", "mode", "dry_run", "min_support",
+                                         "max_contra_permille", "reserved")]
+
+
+class GridMergeBatch(C.Structure):
+    _fields_ = [("n_pairs", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, _VP) for n in ("src", "src_origin", "src_index", "dst", "dst_origin", "xform", "stats", "flags")]
+
+
 assert C.sizeof(ChunkModel) == 112
 assert C.sizeof(LandmarkRec) == 56
 
@@ -248,6 +260,7 @@ EXPORTS = [
     "lslam_relocprior_abi_sizes", "lslam_relocprior_params_default", "lslam_map_relocalize_prior",
     "lslam_page_abi_sizes", "lslam_page_params_default", "lslam_grid_recentre_paged", "lslam_grid_page_flush",
     "lslam_grid_page_load",
+    "lslam_gridmerge_abi_sizes", "lslam_gridmerge_params_default", "lslam_grid_merge",
 ]
 
 _lib = None
@@ -353,6 +366,9 @@ def load():
                                       C.c_int),
         "lslam_grid_page_flush": ([_VP, P(PageBatch), _VP, P(GridParams), P(PageParams)], C.c_int),
         "lslam_grid_page_load": ([_VP, P(PageBatch), _VP, P(GridParams), P(PageParams)], C.c_int),
+        "lslam_gridmerge_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_gridmerge_params_default": ([P(GridMergeParams)], C.c_int),
+        "lslam_grid_merge": ([_VP, P(GridMergeBatch), P(GridParams), P(GridMergeParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -405,6 +421,7 @@ _ABI_SIZES = [
     ("lslam_fieldfuse_abi_sizes", (FieldFuseParams, FieldFuseBatch)),
     ("lslam_relocprior_abi_sizes", (RelocPriorParams, RelocPriorBatch)),
     ("lslam_page_abi_sizes", (PageParams, PageBatch)),
+    ("lslam_gridmerge_abi_sizes", (GridMergeParams, GridMergeBatch)),
 ]
 
 
@@ -468,6 +485,7 @@ fieldalign_params = _params_factory("fieldalign", FieldAlignParams)
 fieldfuse_params = _params_factory("fieldfuse", FieldFuseParams)
 relocprior_params = _params_factory("relocprior", RelocPriorParams)
 page_params = _params_factory("page", PageParams)
+gridmerge_params = _params_factory("gridmerge", GridMergeParams)
 
 
 def ukf_params(n_landmarks, **kw):

@@ -17,7 +17,9 @@
 //   are lslam_fieldalign_core.h, plain C++), lslam_fieldfuse.h (the alignment fused into the filter; its
 //   3 x 3 algebra is lslam_fieldfuse_core.h, plain C++), lslam_relocprior.h (relocalisation over an
 //   admissible set: the free-space prior and the search window), lslam_page.h (the paged rolling
-//   grid: a canvas behind each window; its strips and their clipping are lslam_page_plan.h, plain C++);
+//   grid: a canvas behind each window; its strips and their clipping are lslam_page_plan.h, plain C++),
+//   lslam_gridmerge.h (the map merge: one grid gathered into another's frame, gated and added; its
+//   tiles, gather arithmetic, classes and merged value are lslam_gridmerge_plan.h, plain C++);
 // the host side is included at the foot:
 //   lslam_hazards.h  which waits a call's producer needs (plain C++, no HIP)
 //   lslam_ctx.h      lslam_ctx, its grow-only device buffers and timers, create / destroy,
@@ -3083,6 +3085,9 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
 #include "lslam_relocprior.h"
 // the paged rolling grid's kernels, templates built on the recentre kernel's device functions: the newest
 #include "lslam_page.h"
+// the map merge's kernel, a template: the newest header; its place in the code object is launch_gridmerge's
+// (lslam_launch_map.h), directly ahead of the relocalisation priors' three kernels
+#include "lslam_gridmerge.h"
 
 // ------------------------------------------------------------------------
 // host side: the context, then the launchers and entry points

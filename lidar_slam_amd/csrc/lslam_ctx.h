@@ -440,6 +440,12 @@ int lslam_page_abi_sizes(int64_t *sizes, int n) {
     return 2;
 }
 
+int lslam_gridmerge_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[2] = {(int64_t)sizeof(lslam_gridmerge_params), (int64_t)sizeof(lslam_gridmerge_batch)};
+    for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
+    return 2;
+}
+
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
     if (!c || (!dst && n)) return LSLAM_ERR_ARG;
     if (!n) return LSLAM_OK;
@@ -685,6 +691,18 @@ int lslam_page_params_default(lslam_page_params *p) {
     if (!p) return LSLAM_ERR_ARG;
     memset(p, 0, sizeof(*p));
     p->canvas_w = 2048;  // cells: 40.96 m a side at 20 mm, sixteen default windows; 8 MiB a robot
+    return LSLAM_OK;
+}
+
+int lslam_gridmerge_params_default(lslam_gridmerge_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->src_w = 512;
+    p->n_src = 1;
+    p->occ_min = 85;                // one hit: the matchers' and the distance field's threshold
+    p->mode = LSLAM_MERGE_ADD;
+    p->min_support = 64;            // cells: 1.28 m of common wall at 20 mm
+    p->max_contra_permille = 100;   // measured in the L-shaped room (tests/test_gridmerge_ref.py)
     return LSLAM_OK;
 }
 

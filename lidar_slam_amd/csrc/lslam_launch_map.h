@@ -950,6 +950,74 @@ static int launch_fieldfuse(lslam_ctx *c, const lslam_fieldfuse_batch *b, const 
                          {b->nis, n * 8}});
 }
 
+// ---- map merge (lslam_gridmerge.h) ----
+// Between launch_fieldfuse and the relocalisation priors: a kernel template is emitted where it is first used
+// (lslam_launch.h, at this file's include), and tests/test_relocprior_budget.py holds the priors' three kernels
+// to the code object's end.  Here the four instantiations stand directly ahead of those three: every other kernel
+// keeps its bytes and its place, and the three keep their bytes.
+
+static int gridmerge_check_params(const lslam_gridmerge_params *p) {
+    if (!p) return set_err(LSLAM_ERR_ARG, "gridmerge: params is NULL");
+    if (p->src_w < 16 || p->src_w > 2048) return set_err(LSLAM_ERR_ARG, "gridmerge: src_w must be in [16, 2048]");
+    if (p->n_src < 1) return set_err(LSLAM_ERR_ARG, "gridmerge: n_src must be >= 1");
+    if (p->occ_min < -32768 || p->occ_min > 32767) return set_err(LSLAM_ERR_ARG, "gridmerge: occ_min must be in [-32768, 32767]");
+    if (p->mode != LSLAM_MERGE_ADD && p->mode != LSLAM_MERGE_FILL)
+        return set_err(LSLAM_ERR_ARG, "gridmerge: mode must be LSLAM_MERGE_ADD or LSLAM_MERGE_FILL");
+    if (p->dry_run != 0 && p->dry_run != 1) return set_err(LSLAM_ERR_ARG, "gridmerge: dry_run must be 0 or 1");
+    if (p->min_support < 0) return set_err(LSLAM_ERR_ARG, "gridmerge: min_support must be >= 0");
+    if (p->max_contra_permille < 0 || p->max_contra_permille > 1000)
+        return set_err(LSLAM_ERR_ARG, "gridmerge: max_contra_permille must be in [0, 1000]");
+    return LSLAM_OK;
+}
+
+static Reqs gridmerge_reqs(const lslam_gridmerge_batch &b) {
+    return {{{"src", b.src}, {"src_origin", b.src_origin}, {"dst_origin", b.dst_origin}, {"xform", b.xform}},
+            {{"dst", b.dst}, {"stats", b.stats}, {"flags", b.flags}},
+            b.n_pairs,
+            "n_pairs"};
+}
+
+// One workgroup per (pair, slice of its tiles), by slices_for; the statistics, then the merge.
+static int launch_gridmerge(lslam_ctx *c, const lslam_gridmerge_batch *b, const lslam_grid_params *g,
+                            const lslam_gridmerge_params *p) {
+    MergeArgs k;
+    memset(&k, 0, sizeof(k));
+    k.b = *b;
+    k.cell = g->cell;
+    k.inv = 1.0 / g->cell;
+    k.grid_w = g->grid_w;
+    k.src_w = p->src_w;
+    k.n_src = p->n_src;
+    k.occ_min = p->occ_min;
+    k.l_min = g->l_min;
+    k.l_max = g->l_max;
+    k.fill = p->mode == LSLAM_MERGE_FILL ? 1 : 0;
+    k.dry_run = p->dry_run;
+    k.min_support = p->min_support;
+    k.max_permille = p->max_contra_permille;
+    const int64_t n = b->n_pairs;
+    const int nt = merge_tiles(g->grid_w);
+    k.per = merge_slice_tiles(nt, (int)slices_for(c, n, nt));
+    k.n_slices = merge_slices(nt, k.per);
+    int st = check_blocks("gridmerge", n * k.n_slices);
+    if (st) return st;
+    if ((st = note_outs(c, {{b->dst, (size_t)n * (size_t)g->grid_w * (size_t)g->grid_w * 2}, {b->stats, (size_t)n * 32, true},
+                            {b->flags, (size_t)n * 4}})))
+        return st;
+    const dim3 blocks((unsigned)(n * k.n_slices));
+    if (groups16(g->grid_w, b->dst)) {
+        hipLaunchKernelGGL((gridmerge_kernel<8, false>), blocks, dim3(MERGE_TPB), 0, c->stream, k);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL((gridmerge_kernel<8, true>), blocks, dim3(MERGE_TPB), 0, c->stream, k);
+    } else {
+        hipLaunchKernelGGL((gridmerge_kernel<1, false>), blocks, dim3(MERGE_TPB), 0, c->stream, k);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL((gridmerge_kernel<1, true>), blocks, dim3(MERGE_TPB), 0, c->stream, k);
+    }
+    HIPCHK(hipGetLastError());
+    return LSLAM_OK;
+}
+
 // ---- relocalisation priors (lslam_relocprior.h) ----
 // Behind launch_fieldfuse: its three kernel templates are the newest, so they take the code object's end
 // (lslam_launch.h, at this file's include).
@@ -1223,6 +1291,22 @@ int lslam_map_relocalize_prior(lslam_ctx *c, const lslam_relocprior_batch *b, co
     return map_entry(
         "relocprior", c, b, relocprior_reqs, [&] { return relocprior_check_overlap(b, g, q); },
         [&] { return launch_relocprior(c, b, g, m, q, pp); });
+}
+
+// On the main stream, as lslam_grid_update: after the calls that wrote either grid, before the calls that
+// read the destination.
+int lslam_grid_merge(lslam_ctx *c, const lslam_gridmerge_batch *b, const lslam_grid_params *g, const lslam_gridmerge_params *p) {
+    int st = grid_check_params(g);
+    if (st || (st = gridmerge_check_params(p))) return st;
+    return map_entry(
+        "gridmerge", c, b, gridmerge_reqs,
+        [&]() -> int {
+            const size_t sb = (size_t)p->n_src * (size_t)p->src_w * (size_t)p->src_w * 2;
+            const size_t db = (size_t)b->n_pairs * (size_t)g->grid_w * (size_t)g->grid_w * 2;
+            if (ranges_overlap(b->src, sb, b->dst, db)) return set_err(LSLAM_ERR_ARG, "gridmerge: src overlaps dst");
+            return LSLAM_OK;
+        },
+        [&] { return launch_gridmerge(c, b, g, p); });
 }
 
 // (the scratch is sized per call: a call in flight keeps the chunking it was launched with)

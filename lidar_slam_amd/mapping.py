@@ -29,6 +29,9 @@ from .staging import Staging, _Grow
 GRID_BAD_POSE, GRID_CLIPPED = _lib.GRID_BAD_POSE, _lib.GRID_CLIPPED
 RECENTRE_BAD_POSE, RECENTRE_MOVED, RECENTRE_CLEARED = _lib.RECENTRE_BAD_POSE, _lib.RECENTRE_MOVED, _lib.RECENTRE_CLEARED
 PAGE_LOST = _lib.PAGE_LOST
+MERGE_ADD, MERGE_FILL = _lib.MERGE_ADD, _lib.MERGE_FILL
+MERGE_MERGED, MERGE_WEAK, MERGE_CONFLICT = _lib.MERGE_MERGED, _lib.MERGE_WEAK, _lib.MERGE_CONFLICT
+MERGE_SKIPPED, MERGE_BAD_XFORM = _lib.MERGE_SKIPPED, _lib.MERGE_BAD_XFORM
 DIST_OCC, DIST_NOT_FREE, DIST_EMPTY, FIELD_BAD_POSE = _lib.DIST_OCC, _lib.DIST_NOT_FREE, _lib.DIST_EMPTY, _lib.FIELD_BAD_POSE
 FIELDALIGN_BAD_POSE, FIELDALIGN_CONVERGED, FIELDALIGN_SINGULAR = _lib.FIELDALIGN_BAD_POSE, _lib.FIELDALIGN_CONVERGED, _lib.FIELDALIGN_SINGULAR
 FIELDALIGN_FEW, FIELDALIGN_DIVERGED, FIELDALIGN_WEAK = _lib.FIELDALIGN_FEW, _lib.FIELDALIGN_DIVERGED, _lib.FIELDALIGN_WEAK
@@ -47,6 +50,23 @@ def recentre_band_rows(grid_w):
     """Rows of a band of the recentre kernel (lslam_recentre_plan.h recentre_band_rows): as many whole
     rows as 16384 cells hold.  The tests place shifts on its seams."""
     return max(1, min(int(grid_w), 16384 // int(grid_w)))
+
+
+def merge_transform(pose_in_dst, pose_in_src):
+    """The transform (c, s, tx, ty) of ``OccupancyGrid.merge`` from one robot's pose (x, y, theta) known in
+    both map frames, e.g. where it stands in its own map and where ``GridRelocalizer`` placed the same
+    revolution in the other's: it takes the destination's world coordinates to the source's.
+    theta = theta_src - theta_dst, (c, s) = (cos theta, sin theta), t = p_src - R(theta) p_dst.  On the
+    host, in NumPy: [3] and [3] -> [4]; [n, 3] and [n, 3] -> [n, 4].  The library takes these bits as
+    they are."""
+    d, s = np.asarray(pose_in_dst, np.float64), np.asarray(pose_in_src, np.float64)
+    if d.shape != s.shape or d.shape[-1] != 3:
+        raise ValueError("two poses (x, y, theta), or two arrays [n, 3] of them")
+    th = s[..., 2] - d[..., 2]
+    c, sn = np.cos(th), np.sin(th)
+    tx = s[..., 0] - (c * d[..., 0] - sn * d[..., 1])
+    ty = s[..., 1] - (sn * d[..., 0] + c * d[..., 1])
+    return np.stack([c, sn, tx, ty], -1)
 
 
 class OccupancyGrid:
@@ -99,6 +119,8 @@ class OccupancyGrid:
         self._stage = Staging(ctx, R)
         self.steps = 0
         self._shift = self._rflags = None  # recentre's outputs, allocated by its first call
+        self._merge = None  # merge's outputs (stats, flags), allocated by its first call
+        self._merge_snap = None  # the sources' snapshot of a merge from this grid's own buffer
         self.canvas_w = self.canvas = None
         if canvas_w is not None:
             self._init_canvas(int(canvas_w), win)
@@ -232,6 +254,69 @@ class OccupancyGrid:
         p = _lib.GridParams.from_buffer_copy(self.p)
         p.grid_w = self.canvas_w
         return OccupancyGrid(self.ctx, self.R, _view=(p, self.canvas_origin, self.canvas))
+
+    def merge(self, src, xform, src_index=None, mode=MERGE_ADD, dry_run=False, sync=True, **gates):
+        """Fold ``src``'s maps into this grid's (``lslam_grid_merge``): robot m's grid takes source grid
+        ``src_index[m]`` (None: m), resampled under ``xform[m]`` = (c, s, tx, ty), which takes this grid's
+        world coordinates to the source's (``merge_transform`` makes it from one pose known in both
+        frames), checked against what this grid already holds and, if the two agree, added.
+
+        ``src``: another ``OccupancyGrid`` or a ``world()`` view, of any width but of this grid's ``cell``.
+        ``xform``: host [R, 4] (or one row for all) or a float64 ``DeviceArray``; ``src_index``: host
+        integers [R] or an int32 ``DeviceArray``; an index outside 0..src.R-1 skips its robot
+        (``MERGE_SKIPPED``).  ``mode``: ``MERGE_ADD`` adds the source's log-odds (the same evidence merged
+        twice counts twice), ``MERGE_FILL`` writes only cells this grid does not know.  ``dry_run``:
+        statistics and flags only.  ``gates``: occ_min, min_support, max_contra_permille
+        (``lslam_gridmerge_params``; defaults 85, 64, 100): a robot whose source has fewer than
+        ``min_support`` occupied cells next to occupied cells of this grid is ``MERGE_WEAK``, one with more
+        than ``max_contra_permille`` of them in space this grid holds free is ``MERGE_CONFLICT`` (a wrong
+        transform); either keeps its grid bit for bit.
+
+        If ``src`` shares this grid's buffer (a grid merged into itself under a transform), the source
+        grids are first copied to a snapshot allocated by the first such call (``lslam_d2d``): 2 W^2
+        bytes a robot, kept for the grid's life."""
+        ctx, R = self.ctx, self.R
+        if not isinstance(src, OccupancyGrid):
+            raise ValueError("src must be an OccupancyGrid (or a world() view)")
+        if float(src.p.cell) != float(self.p.cell):
+            raise ValueError("src has cell %r, this grid %r: a merge needs the same cell" % (float(src.p.cell), float(self.p.cell)))
+        unknown = set(gates) - {"occ_min", "min_support", "max_contra_permille"}
+        if unknown:
+            raise TypeError("unknown parameters: %s" % ", ".join(sorted(unknown)))
+        q = _lib.gridmerge_params(src_w=src.W, n_src=src.R, mode=int(mode), dry_run=int(bool(dry_run)),
+                                  **{k: int(v) for k, v in gates.items()})
+        # (a range error of params surfaces here, before anything is staged)
+        _lib.call("lslam_grid_merge", ctx, _lib.GridMergeBatch(), self.p, q)
+        dx = self._stage.per_robot("merge_xform", xform, 4, np.float64, "xform")
+        di = None
+        if src_index is not None:
+            if not isinstance(src_index, DeviceArray) and not np.issubdtype(np.asarray(src_index).dtype, np.integer):
+                raise ValueError("src_index must be integers")
+            di = self._stage.per_robot("merge_index", src_index, 1, np.int32, "src_index")
+        if self._merge is None:
+            self._merge = (ctx.empty((R, 8), np.int32), ctx.empty(R, np.int32))
+        slog = src.logodds
+        if slog.addr == self.logodds.addr:
+            if self._merge_snap is None:
+                self._merge_snap = ctx.empty((R, self.W, self.W), np.int16)
+            ctx.copy(self._merge_snap, slog)
+            slog = self._merge_snap
+        b = _lib.GridMergeBatch()
+        b.n_pairs = R
+        b.src, b.src_origin, b.src_index = slog.addr, src.origin.addr, (di.addr if di is not None else None)
+        b.dst, b.dst_origin, b.xform = self.logodds.addr, self.origin.addr, dx.addr
+        b.stats, b.flags = self._merge[0].addr, self._merge[1].addr
+        _lib.call("lslam_grid_merge", ctx, b, self.p, q)
+        if sync:
+            ctx.sync()
+
+    def merge_results(self):
+        """The last ``merge``'s stats [R, 8] (cells on the source map, cells with a source value, supported,
+        contradicted, new, known in both with equal sign, with opposite sign, changed) and flags [R]
+        (``MERGE_*``)."""
+        if self._merge is None:
+            raise ValueError("no merge yet")
+        return {"stats": self._merge[0].download(), "flags": self._merge[1].download()}
 
     def results(self):
         """logodds [R, W, W] int16 (row Y, 0.01 nat) and the last step's rot [R, 2], n_used [R, 2]

@@ -120,6 +120,7 @@ class Staging:
         self.off = ctx.empty(R + 1, np.int32)
         self.pose_buf = ctx.empty((R, 3), np.float64) if pose else None
         self.off_host = np.zeros(R + 1, np.int64)
+        self._per_robot = {}  # per_robot's buffers, by name
 
     def revolution(self, xy, scan_chunk_off, chunk_pt_off):
         """The argument forms of ``OccupancyGrid.step`` -> device (xy, pt_off).  Host points are uploaded
@@ -151,3 +152,22 @@ class Staging:
             raise ValueError("%s must hold n_robots x 3 values" % what)
         self.pose_buf.upload_async(hp.reshape(R, 3))
         return self.pose_buf
+
+    def per_robot(self, name, arr, width, dtype, what):
+        """A per-robot argument of ``width`` items of ``dtype`` -> a device [R, width]: a ``DeviceArray`` is
+        read in place; a host array (one row for all, or a row per robot) is uploaded, as ``pose`` is, to
+        a buffer of this object's kept under ``name`` and allocated by its first use."""
+        R, dtype = self.R, np.dtype(dtype)
+        if isinstance(arr, DeviceArray):
+            if arr.dtype != dtype or arr.nbytes < R * width * dtype.itemsize:
+                raise ValueError("device %s must be %s [n_robots, %d]" % (what, dtype, width))
+            return arr
+        h = np.asarray(arr)
+        if h.size not in (width, R * width):
+            raise ValueError("%s must hold %d values, or n_robots x %d" % (what, width, width))
+        h = np.ascontiguousarray(np.broadcast_to(h.reshape(-1, width), (R, width)), dtype)
+        bufs = self._per_robot
+        if name not in bufs:
+            bufs[name] = self.off.ctx.empty((R, width), dtype)
+        bufs[name].upload_async(h)
+        return bufs[name]
