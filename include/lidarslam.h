@@ -1443,6 +1443,77 @@ int lslam_gridmerge_params_default(lslam_gridmerge_params *p);
 int lslam_grid_merge(lslam_ctx *ctx, const lslam_gridmerge_batch *b, const lslam_grid_params *g,
                      const lslam_gridmerge_params *p);
 
+/* ---- a map as a revolution (lslam_grid_points): flags (lslam_gridpoints_batch.flags) ---- */
+enum {
+    LSLAM_GRIDPOINTS_BAD_ANCHOR = 1, /* a component of anchor or of origin is not finite: no point */
+    LSLAM_GRIDPOINTS_EMPTY = 2,      /* no occupied cell in range: n_out = 0 */
+    LSLAM_GRIDPOINTS_DECIMATED = 4   /* more occupied cells in range than slots: every stride-th was taken */
+};
+/* bands of rows that a grid is cut into at most: the second dimension of lslam_gridpoints_batch.band_counts */
+#define LSLAM_GRIDPOINTS_BANDS 256
+
+/* A map as a revolution (lslam_grid_points), 16 bytes (a multiple of 8 as it stands: no reserved field).
+ * The grid's geometry (grid_w, cell) comes from the lslam_grid_params given with the call. */
+typedef struct lslam_gridpoints_params {
+    double radius;   /* mm: cells whose centre is further from the anchor are left out; > 0 and finite (8000.0) */
+    int32_t occ_min; /* a cell with L >= occ_min is occupied; -32768..32767 (85) */
+    int32_t cap;     /* slots per robot; 1..65536 (1024) */
+} lslam_gridpoints_params;
+
+/* One point set per robot, 72 bytes; all pointers DEVICE memory; all required. */
+typedef struct lslam_gridpoints_batch {
+    int32_t n_robots;
+    int32_t reserved;
+    const int16_t *logodds; /* [R][grid_w][grid_w], row Y: read only */
+    const double *origin;   /* [R][2] world coordinates of the corner of cell (0, 0) */
+    const double *anchor;   /* [R][4] (ax, ay, c, s): the anchor pose's position in the map's world frame, cos and sin of its heading */
+    double *xy;             /* [R][cap][2]: the points in the anchor's frame, (+0.0, +0.0) behind the last */
+    int32_t *pt_off;        /* [R + 1]: r * cap */
+    int32_t *counts;        /* [R][4] (n_occ, n_in, stride, n_out) */
+    int32_t *flags;         /* [R] LSLAM_GRIDPOINTS_* */
+    int32_t *band_counts;   /* [R][LSLAM_GRIDPOINTS_BANDS][2]: scratch, the count pass's (n_occ, n_in) per band */
+} lslam_gridpoints_batch;
+
+/* lslam_abi_sizes for lslam_gridpoints_params, lslam_gridpoints_batch.  Writes min(n, 2) entries, returns 2. */
+int lslam_gridpoints_abi_sizes(int64_t *sizes, int n);
+int lslam_gridpoints_params_default(lslam_gridpoints_params *p);
+
+/* A map as a revolution: the occupied cells of each robot's grid within radius of an anchor pose, as
+ * points in that pose's frame, in the CSR revolution form that lslam_map_relocalize, lslam_map_match,
+ * lslam_field_score, lslam_field_align and lslam_grid_raycast read (xy, pt_off): what a stored map, a
+ * canvas or a map whose robot has gone offers in place of a revolution.  anchor[r] = (ax, ay, c, s): the
+ * bits of c = cos theta and s = sin theta are the caller's; there is no trigonometry in the library.
+ * W = grid_w and cell are g's.  All FP64, every operation rounded on its own (nothing is fused), then
+ * integers; r2 = radius * radius, one product taken on the host.  Per robot r:
+ *   0. pt_off[r] = r * cap for r in 0..R, always (R * cap >= 2^31 is refused: LSLAM_ERR_ARG).
+ *   1. if any of ax, ay, c, s, origin[r] = (ox, oy) is not finite: flags[r] = LSLAM_GRIDPOINTS_BAD_ANCHOR,
+ *      counts[r] all zero, every slot of robot r is (+0.0, +0.0); nothing else happens.
+ *   2. the cells in row-major order, Y outer, X inner.  A cell is occupied iff L[Y][X] >= occ_min.
+ *      wx = ox + ((double)X + 0.5) cell, wy = oy + ((double)Y + 0.5) cell; dx = wx - ax, dy = wy - ay;
+ *      d2 = dx dx + dy dy.  An occupied cell is IN RANGE iff d2 > 0.0 and d2 <= r2 (the cell whose centre
+ *      is the anchor is left out: (0, 0) is the matchers' invalid point).  i is the cell's ordinal among
+ *      the occupied cells in range; n_occ counts the occupied cells, n_in those in range.
+ *   3. stride = max(1, (n_in + cap - 1) / cap).  Cell i is taken iff i % stride == 0, into slot
+ *      j = i / stride; n_out = (n_in + stride - 1) / stride <= cap.
+ *   4. xy[r][j] = ((c dx) + (s dy), (c dy) - (s dx)).  Slots n_out..cap-1 are (+0.0, +0.0): every consumer
+ *      that uses the scan matcher's validity rule skips them.
+ *   5. counts[r] = (n_occ, n_in, stride, n_out); flags[r] = LSLAM_GRIDPOINTS_EMPTY iff n_out == 0, else
+ *      LSLAM_GRIDPOINTS_DECIMATED iff stride > 1, else 0.
+ * The slots are fixed (robot r owns xy[r * cap .. (r + 1) * cap)), so the host knows pt_off without
+ * waiting for the device.  Decimation by stride follows the row-major order: it is not uniform in
+ * space, and a thick wall weighs more than a thin one.  A map seen as a scan has no occlusion.
+ * Two launches on the main stream behind a memset of xy (lslam_gridpoints.h): the count pass writes
+ * (n_occ, n_in) of every band of rows to band_counts, the caller's scratch (2 KiB a robot: the context
+ * holds none for this call, so nothing grows and nothing waits); the write pass takes each band's first
+ * ordinal from the finished counts and stores the taken points in order, without atomics.  Nothing is
+ * written beyond xy[R * cap], pt_off[R + 1], counts[R][4], flags[R] and band_counts.  Runs on the
+ * context's main stream, after every earlier call, with no host synchronisation inside; there is no
+ * timing slot.  g is checked as lslam_grid_update checks it.  Out-of-range parameters and missing
+ * pointers return LSLAM_ERR_ARG (the message names the field), checked before the context is touched;
+ * n_robots == 0 does nothing. */
+int lslam_grid_points(lslam_ctx *ctx, const lslam_gridpoints_batch *b, const lslam_grid_params *g,
+                      const lslam_gridpoints_params *p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,9 @@ lidar_slam_amd.odometry.ScanMatcher / LidarOdometry (LiDAR-only odometry: wheel 
 lidar_slam_amd.mapping.OccupancyGrid (per-robot log-odds grids from the revolutions and the filter's poses;
 ``recentre`` rolls a grid under a robot that nears its edge; ``merge`` folds another robot's map into it under
 ``mapping.merge_transform``, gated on the two maps' agreement),
+lidar_slam_amd.mapping.GridScan (a map as a revolution: a grid's occupied cells about an anchor pose, on the device,
+in the form every matcher takes) and lidar_slam_amd.mapping.align_maps (that scan relocalised in another map: the
+merge's transform found from the two maps alone),
 lidar_slam_amd.mapping.GridRayCaster (the grid read beam by beam: expected returns, beam classes, the dynamic-object mask),
 lidar_slam_amd.mapping.DistanceField (the grid's exact distance field: clearance, a revolution's distance to the map,
 its Gauss-Newton alignment there, and ``fuse``: that alignment as a gated Kalman update of the filter),

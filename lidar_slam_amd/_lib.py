@@ -49,6 +49,8 @@ FIELD_BAD_POSE = 1
 FIELDFUSE_OUTLIER, FIELDFUSE_BAD_COV = 64, 128
 MERGE_ADD, MERGE_FILL = 0, 1  # lslam_gridmerge_params.mode
 MERGE_MERGED, MERGE_WEAK, MERGE_CONFLICT, MERGE_SKIPPED, MERGE_BAD_XFORM = 1, 2, 4, 8, 16
+GRIDPOINTS_BAD_ANCHOR, GRIDPOINTS_EMPTY, GRIDPOINTS_DECIMATED = 1, 2, 4
+GRIDPOINTS_BANDS = 256  # LSLAM_GRIDPOINTS_BANDS: the second dimension of lslam_gridpoints_batch.band_counts
 
 
 class HIPLibraryError(RuntimeError):
@@ -234,6 +236,15 @@ class GridMergeBatch(C.Structure):
                [(n, _VP) for n in ("src", "src_origin", "src_index", "dst", "dst_origin", "xform", "stats", "flags")]
 
 
+class GridPointsParams(C.Structure):
+    _fields_ = [("radius", C.c_double), ("occ_min", C.c_int32), ("cap", C.c_int32)]
+
+
+class GridPointsBatch(C.Structure):
+    _fields_ = [("n_robots", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, _VP) for n in ("logodds", "origin", "anchor", "xy", "pt_off", "counts", "flags", "band_counts")]
+
+
 assert C.sizeof(ChunkModel) == 112
 assert C.sizeof(LandmarkRec) == 56
 
@@ -261,6 +272,7 @@ EXPORTS = [
     "lslam_page_abi_sizes", "lslam_page_params_default", "lslam_grid_recentre_paged", "lslam_grid_page_flush",
     "lslam_grid_page_load",
     "lslam_gridmerge_abi_sizes", "lslam_gridmerge_params_default", "lslam_grid_merge",
+    "lslam_gridpoints_abi_sizes", "lslam_gridpoints_params_default", "lslam_grid_points",
 ]
 
 _lib = None
@@ -369,6 +381,9 @@ def load():
         "lslam_gridmerge_abi_sizes": ([P(i64), C.c_int], C.c_int),
         "lslam_gridmerge_params_default": ([P(GridMergeParams)], C.c_int),
         "lslam_grid_merge": ([_VP, P(GridMergeBatch), P(GridParams), P(GridMergeParams)], C.c_int),
+        "lslam_gridpoints_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_gridpoints_params_default": ([P(GridPointsParams)], C.c_int),
+        "lslam_grid_points": ([_VP, P(GridPointsBatch), P(GridParams), P(GridPointsParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -422,6 +437,7 @@ _ABI_SIZES = [
     ("lslam_relocprior_abi_sizes", (RelocPriorParams, RelocPriorBatch)),
     ("lslam_page_abi_sizes", (PageParams, PageBatch)),
     ("lslam_gridmerge_abi_sizes", (GridMergeParams, GridMergeBatch)),
+    ("lslam_gridpoints_abi_sizes", (GridPointsParams, GridPointsBatch)),
 ]
 
 
@@ -486,6 +502,7 @@ fieldfuse_params = _params_factory("fieldfuse", FieldFuseParams)
 relocprior_params = _params_factory("relocprior", RelocPriorParams)
 page_params = _params_factory("page", PageParams)
 gridmerge_params = _params_factory("gridmerge", GridMergeParams)
+gridpoints_params = _params_factory("gridpoints", GridPointsParams)
 
 
 def ukf_params(n_landmarks, **kw):

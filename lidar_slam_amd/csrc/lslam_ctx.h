@@ -446,6 +446,12 @@ int lslam_gridmerge_abi_sizes(int64_t *sizes, int n) {
     return 2;
 }
 
+int lslam_gridpoints_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[2] = {(int64_t)sizeof(lslam_gridpoints_params), (int64_t)sizeof(lslam_gridpoints_batch)};
+    for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
+    return 2;
+}
+
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
     if (!c || (!dst && n)) return LSLAM_ERR_ARG;
     if (!n) return LSLAM_OK;
@@ -703,6 +709,15 @@ int lslam_gridmerge_params_default(lslam_gridmerge_params *p) {
     p->mode = LSLAM_MERGE_ADD;
     p->min_support = 64;            // cells: 1.28 m of common wall at 20 mm
     p->max_contra_permille = 100;   // measured in the L-shaped room (tests/test_gridmerge_ref.py)
+    return LSLAM_OK;
+}
+
+int lslam_gridpoints_params_default(lslam_gridpoints_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->radius = 8000.0;  // the grid's default max_range: the matchers drop what lies further
+    p->occ_min = 85;     // one hit: the matchers' and the merge's threshold
+    p->cap = 1024;       // slots: the L-shaped room's 827 cells in range fit (tests/test_gridpoints_ref.py)
     return LSLAM_OK;
 }
 

@@ -950,8 +950,62 @@ static int launch_fieldfuse(lslam_ctx *c, const lslam_fieldfuse_batch *b, const 
                          {b->nis, n * 8}});
 }
 
+// ---- a map as a revolution (lslam_gridpoints.h) ----
+// Between launch_fieldfuse and launch_gridmerge: a kernel template is emitted where it is first used, and
+// tests/test_gridmerge_budget.py holds the merge's four kernels to the places -7..-4 of the code object.  Here the
+// four instantiations stand directly ahead of those four: every other kernel keeps its bytes and its place.
+
+static int gridpoints_check_params(const lslam_gridpoints_params *p) {
+    if (!p) return set_err(LSLAM_ERR_ARG, "gridpoints: params is NULL");
+    if (!(p->radius > 0) || !std::isfinite(p->radius)) return set_err(LSLAM_ERR_ARG, "gridpoints: radius must be > 0 and finite");
+    if (p->occ_min < -32768 || p->occ_min > 32767) return set_err(LSLAM_ERR_ARG, "gridpoints: occ_min must be in [-32768, 32767]");
+    if (p->cap < 1 || p->cap > 65536) return set_err(LSLAM_ERR_ARG, "gridpoints: cap must be in [1, 65536]");
+    return LSLAM_OK;
+}
+
+static Reqs gridpoints_reqs(const lslam_gridpoints_batch &b) {
+    return {{{"logodds", b.logodds}, {"origin", b.origin}, {"anchor", b.anchor}},
+            {{"xy", b.xy}, {"pt_off", b.pt_off}, {"counts", b.counts}, {"flags", b.flags}, {"band_counts", b.band_counts}},
+            b.n_robots};
+}
+
+// One wave per (robot, band of rows): eight waves a SIMD when the robots alone do not give them, at most
+// GP_BANDS bands.  The memset of xy, the count pass, the write pass.
+static int launch_gridpoints(lslam_ctx *c, const lslam_gridpoints_batch *b, const lslam_grid_params *g,
+                             const lslam_gridpoints_params *p) {
+    GridPointsArgs k;
+    memset(&k, 0, sizeof(k));
+    k.b = *b;
+    k.cell = g->cell;
+    k.r2 = p->radius * p->radius;
+    k.grid_w = g->grid_w;
+    k.occ_min = p->occ_min;
+    k.cap = p->cap;
+    k.n_robots = b->n_robots;
+    const int64_t n = b->n_robots;
+    k.rows = gp_band_rows(g->grid_w, (int)std::min<int64_t>((32 * (int64_t)c->n_cus + n - 1) / n, GP_BANDS));
+    k.n_bands = gp_bands(g->grid_w, k.rows);
+    int st = check_blocks("gridpoints", n * k.n_bands);
+    if (st) return st;
+    if ((st = note_outs(c, {{b->xy, (size_t)n * (size_t)p->cap * 16, true}, {b->pt_off, ((size_t)n + 1) * 4}, {b->counts, (size_t)n * 16},
+                            {b->flags, (size_t)n * 4}, {b->band_counts, (size_t)n * GP_BANDS * 8}})))
+        return st;
+    const dim3 blocks((unsigned)(n * k.n_bands));
+    if (groups16(g->grid_w, b->logodds)) {
+        hipLaunchKernelGGL((gridpoints_kernel<8, false>), blocks, dim3(GP_WAVE), 0, c->stream, k);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL((gridpoints_kernel<8, true>), blocks, dim3(GP_WAVE), 0, c->stream, k);
+    } else {
+        hipLaunchKernelGGL((gridpoints_kernel<1, false>), blocks, dim3(GP_WAVE), 0, c->stream, k);
+        HIPCHK(hipGetLastError());
+        hipLaunchKernelGGL((gridpoints_kernel<1, true>), blocks, dim3(GP_WAVE), 0, c->stream, k);
+    }
+    HIPCHK(hipGetLastError());
+    return LSLAM_OK;
+}
+
 // ---- map merge (lslam_gridmerge.h) ----
-// Between launch_fieldfuse and the relocalisation priors: a kernel template is emitted where it is first used
+// Between launch_gridpoints and the relocalisation priors: a kernel template is emitted where it is first used
 // (lslam_launch.h, at this file's include), and tests/test_relocprior_budget.py holds the priors' three kernels
 // to the code object's end.  Here the four instantiations stand directly ahead of those three: every other kernel
 // keeps its bytes and its place, and the three keep their bytes.
@@ -1307,6 +1361,22 @@ int lslam_grid_merge(lslam_ctx *c, const lslam_gridmerge_batch *b, const lslam_g
             return LSLAM_OK;
         },
         [&] { return launch_gridmerge(c, b, g, p); });
+}
+
+// On the main stream, as lslam_grid_update: after the calls that wrote the grids, before the calls that read
+// the points.
+int lslam_grid_points(lslam_ctx *c, const lslam_gridpoints_batch *b, const lslam_grid_params *g, const lslam_gridpoints_params *p) {
+    int st = grid_check_params(g);
+    if (st || (st = gridpoints_check_params(p))) return st;
+    return map_entry(
+        "gridpoints", c, b, gridpoints_reqs,
+        [&]() -> int {
+            // pt_off is 32 bits wide
+            if ((int64_t)b->n_robots * (int64_t)p->cap >= ((int64_t)1 << 31))
+                return set_err(LSLAM_ERR_ARG, "gridpoints: n_robots * cap must be below 2^31");
+            return LSLAM_OK;
+        },
+        [&] { return launch_gridpoints(c, b, g, p); });
 }
 
 // (the scratch is sized per call: a call in flight keeps the chunking it was launched with)

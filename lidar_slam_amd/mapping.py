@@ -32,6 +32,7 @@ PAGE_LOST = _lib.PAGE_LOST
 MERGE_ADD, MERGE_FILL = _lib.MERGE_ADD, _lib.MERGE_FILL
 MERGE_MERGED, MERGE_WEAK, MERGE_CONFLICT = _lib.MERGE_MERGED, _lib.MERGE_WEAK, _lib.MERGE_CONFLICT
 MERGE_SKIPPED, MERGE_BAD_XFORM = _lib.MERGE_SKIPPED, _lib.MERGE_BAD_XFORM
+GRIDPOINTS_BAD_ANCHOR, GRIDPOINTS_EMPTY, GRIDPOINTS_DECIMATED = _lib.GRIDPOINTS_BAD_ANCHOR, _lib.GRIDPOINTS_EMPTY, _lib.GRIDPOINTS_DECIMATED
 DIST_OCC, DIST_NOT_FREE, DIST_EMPTY, FIELD_BAD_POSE = _lib.DIST_OCC, _lib.DIST_NOT_FREE, _lib.DIST_EMPTY, _lib.FIELD_BAD_POSE
 FIELDALIGN_BAD_POSE, FIELDALIGN_CONVERGED, FIELDALIGN_SINGULAR = _lib.FIELDALIGN_BAD_POSE, _lib.FIELDALIGN_CONVERGED, _lib.FIELDALIGN_SINGULAR
 FIELDALIGN_FEW, FIELDALIGN_DIVERGED, FIELDALIGN_WEAK = _lib.FIELDALIGN_FEW, _lib.FIELDALIGN_DIVERGED, _lib.FIELDALIGN_WEAK
@@ -673,3 +674,123 @@ class DistanceField:
         beam-end-point score, in squared cells."""
         s = self.stats.download()
         return np.where(s[:, 1] > 0, s[:, 0] / np.maximum(s[:, 1], 1), 0.0)
+
+
+class GridScan:
+    """``grid``'s maps as revolutions (``lslam_grid_points``): per robot the occupied cells (L >= ``occ_min``)
+    within ``radius`` of an anchor pose, as points in that pose's frame, on the device.  It is what a
+    stored map, a ``world()`` canvas or the map of a robot that has gone offers where a revolution is asked
+    for::
+
+        scan = GridScan(other_grid)
+        scan.step()                                            # anchors: the grids' centres, heading 0
+        reloc.relocalize(scan.input, grid=grid)                # where those anchors lie in ``grid``
+        xform = merge_transform(reloc.results()["pose"], scan.anchor_pose)
+        grid.merge(other_grid, xform)                          # (``align_maps`` is these four lines)
+
+    ``cap``: slots per robot (1..65536); a robot with more cells in range keeps every stride-th in
+    row-major order (``GRIDPOINTS_DECIMATED``; not uniform in space).  ``radius`` (mm) defaults to the
+    grid's ``max_range``; a larger one is refused, since the matchers drop points beyond it.  A map seen as
+    a scan has no occlusion and a thick wall weighs more than a thin one.  The grid's device buffers are
+    read in place, and nothing of them comes to the host."""
+
+    def __init__(self, grid: OccupancyGrid, cap=1024, radius=None, occ_min=85):
+        if not isinstance(grid, OccupancyGrid):
+            raise ValueError("grid must be an OccupancyGrid (or a world() view)")
+        self.grid, self.ctx, self.R = grid, grid.ctx, grid.R
+        ctx, R = self.ctx, self.R
+        radius = float(grid.p.max_range) if radius is None else float(radius)
+        if radius > float(grid.p.max_range):
+            raise ValueError("radius %r is beyond the grid's max_range %r: the matchers drop those points" % (radius, float(grid.p.max_range)))
+        self.p = _lib.gridpoints_params(radius=radius, occ_min=int(occ_min), cap=int(cap))
+        # (a range error of params surfaces here, before anything is allocated)
+        _lib.call("lslam_grid_points", ctx, _lib.GridPointsBatch(), grid.p, self.p)
+        cap = self.cap = int(self.p.cap)
+        if R * cap >= 2 ** 31:
+            raise ValueError("n_robots * cap must be below 2^31")
+        self.xy = ctx.empty((R * cap, 2), np.float64)
+        self.pt_off = ctx.empty(R + 1, np.int32)
+        self.counts = ctx.empty((R, 4), np.int32)
+        self.flags = ctx.empty(R, np.int32)
+        self._bands = ctx.empty((R, _lib.GRIDPOINTS_BANDS, 2), np.int32)  # the count pass's scratch
+        self._stage = Staging(ctx, R, pose=False)
+        self.input = staging.MapInput()
+        self.input.xy = self.xy
+        self.input.sco = np.arange(R + 1, dtype=np.int64)
+        self.input.cpo = np.arange(R + 1, dtype=np.int64) * cap
+        self.anchor_pose = None  # host [R, 3] of the last step, None after a step with a device anchor
+        self.steps = 0
+
+    def step(self, anchor=None, sync=True):
+        """The points of the grids as they now stand.  ``anchor``: host poses [R, 3] (x, y, theta) in each
+        map's world frame, or one pose for all, from which (ax, ay, cos theta, sin theta) are made on the
+        host in NumPy; or a float64 ``DeviceArray`` [R, 4] of (ax, ay, c, s), used in place; default: each
+        grid's centre with theta = 0 (which reads ``origin_host``: after a ``recentre`` that waits for the
+        stream)."""
+        ctx, R, g = self.ctx, self.R, self.grid
+        if isinstance(anchor, DeviceArray):
+            self.anchor_pose = None
+            da = self._stage.per_robot("anchor", anchor, 4, np.float64, "anchor")
+        else:
+            if anchor is None:
+                pose = np.concatenate([g.origin_host + 0.5 * g.W * float(g.p.cell), np.zeros((R, 1))], 1)
+            else:
+                pose = np.asarray(anchor, np.float64)
+                if pose.size not in (3, 3 * R):
+                    raise ValueError("anchor must hold 3 values (x, y, theta), or n_robots x 3")
+                pose = np.broadcast_to(pose.reshape(-1, 3), (R, 3))
+            self.anchor_pose = np.array(pose, np.float64)
+            p = self.anchor_pose
+            da = self._stage.per_robot("anchor", np.stack([p[:, 0], p[:, 1], np.cos(p[:, 2]), np.sin(p[:, 2])], -1), 4,
+                                       np.float64, "anchor")
+        b = _lib.GridPointsBatch()
+        b.n_robots = R
+        b.logodds, b.origin, b.anchor = g.logodds.addr, g.origin.addr, da.addr
+        b.xy, b.pt_off, b.counts, b.flags = self.xy.addr, self.pt_off.addr, self.counts.addr, self.flags.addr
+        b.band_counts = self._bands.addr
+        _lib.call("lslam_grid_points", ctx, b, g.p, self.p)
+        self.steps += 1
+        if sync:
+            ctx.sync()
+
+    def results(self):
+        """The last step's xy [R, cap, 2] (robot r's points are the first ``counts[r, 3]``, zeros behind
+        them), counts [R, 4] (occupied cells, those in range, stride, points) and flags [R]
+        (``GRIDPOINTS_*``)."""
+        if not self.steps:
+            raise ValueError("no step yet")
+        return {"xy": self.xy.download().reshape(self.R, self.cap, 2), "counts": self.counts.download(),
+                "flags": self.flags.download()}
+
+
+def align_maps(dst, src, relocalizer, scan=None, anchor=None, **reloc_kw):
+    """The transform that ``dst.merge(src, xform)`` needs, found from the two maps alone: ``scan`` (a
+    ``GridScan`` of ``src``, made with its defaults if None) is stepped at ``anchor`` (host poses, as
+    ``GridScan.step``; default: the centres of ``src``'s grids), ``relocalizer`` (a ``GridRelocalizer`` of as
+    many robots) finds every anchor in ``dst``'s map m (``relocalize(scan.input, grid=dst, **reloc_kw)``:
+    ``field=`` and ``window=`` pass through), and ``merge_transform`` makes xform from the found pose and the
+    anchor's, on the host (24 bytes a robot; the call synchronises).
+
+    Returns xform [R, 4], pose [R, 3] (the anchors in ``dst``'s frames), flags [R] (the relocaliser's
+    ``RELOC_*``) and counts [R, 4] (``GridScan.results``).  A LOST or AMBIGUOUS pair has a NaN pose and
+    hence a NaN transform, which ``dst.merge`` answers with ``MERGE_BAD_XFORM`` and leaves that destination
+    bit for bit: that is the one mechanism, nothing is filtered here.  The relocaliser's ``min_permille``
+    asks that share of the source's walls within the scan's radius to exist in ``dst``: for maps that
+    overlap less, lower it, or move the anchor and shrink the radius to the shared part."""
+    if not isinstance(dst, OccupancyGrid) or not isinstance(src, OccupancyGrid):
+        raise ValueError("dst and src must be OccupancyGrids (or world() views)")
+    if not (src.R == dst.R == relocalizer.R):
+        raise ValueError("src holds %d robots, dst %d, the relocalizer %d" % (src.R, dst.R, relocalizer.R))
+    if float(src.p.cell) != float(dst.p.cell):
+        raise ValueError("src has cell %r, dst %r: aligning needs the same cell" % (float(src.p.cell), float(dst.p.cell)))
+    if scan is None:
+        scan = GridScan(src)
+    elif not isinstance(scan, GridScan) or scan.grid is not src:
+        raise ValueError("scan must be a GridScan of src")
+    if isinstance(anchor, DeviceArray):
+        raise ValueError("align_maps needs the anchor on the host: merge_transform reads it there")
+    scan.step(anchor, sync=False)
+    relocalizer.relocalize(scan.input, grid=dst, sync=True, **reloc_kw)
+    res = relocalizer.results()
+    return {"xform": merge_transform(res["pose"], scan.anchor_pose), "pose": res["pose"], "flags": res["flags"],
+            "counts": scan.counts.download()}
