@@ -49,6 +49,33 @@ extern "C" int lslam_debug_set_stamps(unsigned long long *dev_buf) {
 }
 #endif
 
+// The fused scan kernel (the MT19937 fix-up) runs every chunk of a replayed scan through mt_draws
+// with the chunk's OWN mt_nslot(n), and mt_nslot is not monotonic in n: 64 slots at n = 3, 8 from 17
+// to 512 points, 2 above.  Its draw-resolution tables (j1s: one word per slot; nxt: n words per slot)
+// must hold the worst chunk size up to the batch's largest, not the largest's own.
+struct MtTables {
+    int slots;    // max mt_nslot(n)
+    int entries;  // max mt_nslot(n) * n
+};
+static MtTables mt_tables_upto(int N) {
+    constexpr int SMALL = 512;  // mt_resolve_batch's threshold: above it mt_nslot(n) = 2
+    static const std::vector<MtTables> pre = [] {
+        std::vector<MtTables> v(SMALL + 1, MtTables{1, 1});
+        for (int n = 1; n <= SMALL; n++) {
+            const int s = mt_nslot(n);
+            v[n].slots = std::max(v[n - 1].slots, s);
+            v[n].entries = std::max(v[n - 1].entries, s * n);
+        }
+        return v;
+    }();
+    MtTables m = pre[std::min(std::max(N, 1), SMALL)];
+    if (N > SMALL) {
+        m.slots = std::max(m.slots, mt_nslot(N));
+        m.entries = std::max(m.entries, mt_nslot(N) * N);
+    }
+    return m;
+}
+
 static int build_args(KArgs &k, const lslam_scan_batch *b, const lslam_ransac_params *p, const lslam_ukf_params *u,
                       int mode, int &lds) {
     memset(&k, 0, sizeof(k));
@@ -90,13 +117,14 @@ static int build_args(KArgs &k, const lslam_scan_batch *b, const lslam_ransac_pa
         k.off_key = off; off += align16(4 * 624);
         // phase-exclusive scratch shares one region: the draw-resolution tables
         // (draw generation), then the tie sums (selection)
-        const int nxt_bytes = 4 * mt_nslot(N) * N;
+        const MtTables mtt = mt_tables_upto(N);
+        const int nxt_bytes = 4 * mtt.entries;
         const int uni_bytes = max(nxt_bytes, 8 * (T > 0 ? T : 1));
         k.off_ring = off;
         k.off_tsum = off;
         off += align16(uni_bytes);
         k.off_j1 = off;
-        off += align16(4 * mt_nslot(N));
+        off += align16(4 * mtt.slots);
         k.off_draws = off; off += align16(8 * (T + 1));
         k.off_cnt = off; off += align16(4 * (T > 0 ? T : 1));
         k.off_tied = off; off += align16(4 * (T > 0 ? T : 1));
@@ -158,7 +186,13 @@ static int build_args(KArgs &k, const lslam_scan_batch *b, const lslam_ransac_pa
         k.ukf.flags = u->flags;
     }
     lds = off;
-    if (lds > 160 * 1024) return set_err(LSLAM_ERR_CAPACITY, "chunk/trial/landmark sizes exceed the 160 KiB LDS");
+    // The MODE_RANSAC layout is the MT19937 fix-up kernel's (run_split).  With Philox or explicit
+    // hypotheses no kernel is launched with it: the consensus kernels lay out and check their own LDS
+    // (layout_chunk, layout_select), so its size refuses nothing there beyond the points themselves.
+    const bool unused = mode == MODE_RANSAC && p && p->hyp_source != LSLAM_HYP_MT19937 &&
+                        (int64_t)16 * N <= 160 * 1024;
+    if (lds > 160 * 1024 && !unused)
+        return set_err(LSLAM_ERR_CAPACITY, "chunk/trial/landmark sizes exceed the 160 KiB LDS");
     return LSLAM_OK;
 }
 
