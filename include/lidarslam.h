@@ -1514,6 +1514,107 @@ int lslam_gridpoints_params_default(lslam_gridpoints_params *p);
 int lslam_grid_points(lslam_ctx *ctx, const lslam_gridpoints_batch *b, const lslam_grid_params *g,
                       const lslam_gridpoints_params *p);
 
+/* ---- pose-graph optimisation (lslam_pose_graph): flags (lslam_posegraph_batch.flags) ---- */
+enum {
+    LSLAM_POSEGRAPH_EMPTY = 1,     /* fewer than two nodes or no edge: nothing is evaluated, pose_out is pose */
+    LSLAM_POSEGRAPH_BAD_GRAPH = 2, /* a count out of range, an edge on a node that is not there, or a value that is not finite: pose_out is pose */
+    LSLAM_POSEGRAPH_CONVERGED = 4, /* a step fell below eps_t and eps_r at every node */
+    LSLAM_POSEGRAPH_SINGULAR = 8,  /* a pivot of the solve is not finite and > 0, or a stepped pose is not finite: pose_out is pose */
+    LSLAM_POSEGRAPH_DIVERGED = 16  /* chi2 of the last evaluation is not <= that of the first: pose_out is pose */
+};
+
+/* Pose-graph optimisation (lslam_pose_graph), 48 bytes. */
+typedef struct lslam_posegraph_params {
+    double damp_t;     /* 1/mm^2, added to the x and y diagonal of every free node; >= 0 and finite (1e-6) */
+    double damp_r;     /* 1/rad^2, added to the theta diagonal; >= 0 and finite (1e-3) */
+    double eps_t;      /* mm: a step below it at every node (with eps_r) ends the iteration; >= 0 and finite (0.01) */
+    double eps_r;      /* rad; >= 0 and finite (1e-5) */
+    int32_t max_nodes; /* N_cap: the node dimension of pose, pose_out and trace; 2..64 (48) */
+    int32_t max_edges; /* E_cap: the edge dimension of edge_ij, edge_z, edge_info and edge_chi2; 1..1024 (256) */
+    int32_t n_iter;    /* Gauss-Newton steps at most; 0..32 (10) */
+    int32_t reserved;
+} lslam_posegraph_params;
+
+/* One graph per robot, 104 bytes; all pointers DEVICE memory; all required.  pose and pose_out are
+ * NODE-MAJOR: slab k is a contiguous [n_graphs][3], what every map-side call takes as its pose. */
+typedef struct lslam_posegraph_batch {
+    int32_t n_graphs;
+    int32_t reserved;
+    const int32_t *n_nodes;  /* [G] */
+    const int32_t *n_edges;  /* [G] */
+    const double *pose;      /* [N_cap][G][3] (x, y in mm, theta in rad) */
+    const int32_t *edge_ij;  /* [G][E_cap][2] */
+    const double *edge_z;    /* [G][E_cap][3]: the pose of node j in node i's frame */
+    const double *edge_info; /* [G][E_cap][6]: the symmetric Omega in i's frame as xx, xy, xt, yy, yt, tt (1/mm^2, 1/(mm rad), 1/rad^2) */
+    double *pose_out;        /* [N_cap][G][3]; may be pose */
+    double *trace;           /* [G][n_iter + 1][N_cap][2] (cos, sin) of every node at every evaluation, zeros beyond */
+    double *chi2;            /* [G][2]: of the first and of the last evaluation */
+    double *edge_chi2;       /* [G][E_cap]: per edge at the last evaluation */
+    int32_t *iters;          /* [G] steps taken */
+    int32_t *flags;          /* [G] LSLAM_POSEGRAPH_* */
+} lslam_posegraph_batch;
+
+/* lslam_abi_sizes for lslam_posegraph_params, lslam_posegraph_batch.  Writes min(n, 2) entries, returns 2. */
+int lslam_posegraph_abi_sizes(int64_t *sizes, int n);
+int lslam_posegraph_params_default(lslam_posegraph_params *p);
+
+/* Pose-graph optimisation: per robot one graph whose nodes are keyframe poses (x, y, theta) and whose
+ * edges are relative-pose measurements (odometry between consecutive keyframes, loop closures between
+ * distant ones), solved by damped Gauss-Newton with node 0 held as the gauge.  The corrected poses come
+ * out node-major, so that a map can be redrawn from them slab by slab (lslam_grid_update).
+ * N_cap = max_nodes, E_cap = max_edges.  All FP64, every operation rounded on its own (nothing is
+ * fused).  Per graph, N = n_nodes and E = n_edges; x_i = (x_i, y_i, theta_i):
+ *   0. Checks.  If N < 0, E < 0, N > N_cap or E > E_cap: LSLAM_POSEGRAPH_BAD_GRAPH.  Else if N < 2 or
+ *      E = 0: LSLAM_POSEGRAPH_EMPTY.  Else LSLAM_POSEGRAPH_BAD_GRAPH iff an edge e < E has i = j or an
+ *      index outside 0..N-1, or a component of a pose of nodes 0..N-1, of a z or of an Omega of edges
+ *      0..E-1 is not finite.  With either flag pose_out = pose bit for bit (all N_cap slabs, copied as
+ *      64-bit words), flags is that one flag, and trace, chi2, edge_chi2 and iters of the graph are
+ *      zero; nothing else happens.
+ *   1. Evaluation k = 0, 1, ... at the poses as they then stand.  (c_i, s_i) = the library's cos and
+ *      sin of theta_i, written to trace[g][k][i] for i < N; the written bits are the definition's
+ *      input.  Per edge e = (i, j, z, Omega):
+ *        dx = x_j - x_i, dy = y_j - y_i; ux = (c_i dx) + (s_i dy), uy = (c_i dy) - (s_i dx);
+ *        e0 = ux - z0, e1 = uy - z1, e2 = remainder((theta_j - theta_i) - z2, 6.283185307179586), the
+ *        IEEE operation, which is exact;
+ *        A = de/dx_i = [[-c, -s, uy], [s, -c, -ux], [+0, +0, -1]],
+ *        B = de/dx_j = [[c, s, +0], [-s, c, +0], [+0, +0, 1]];
+ *        MA = Omega A, MB = Omega B, w = Omega e, chi_e = e^T w, and the contributions A^T MA to block
+ *        (i, i), A^T MB to block (i, j), its transpose bit for bit to (j, i), B^T MB to (j, j), A^T w
+ *        to g_i and B^T w to g_j.  Every element of these 3-term products is (t0 + t1) + t2 over the
+ *        inner index 0, 1, 2, with all three products formed (the zeros and ones of A and B too).
+ *      Every element of the lower triangle of H and of g is the sum, from +0.0, of its contributions in
+ *      ascending e; chi2_k is the sum of chi_e from +0.0 in ascending e; edge_chi2[g][e] = chi_e of the
+ *      last evaluation made.  The iteration ends here if k = n_iter or the step before set
+ *      LSLAM_POSEGRAPH_CONVERGED.
+ *   2. Step k.  Node 0's rows and columns are dropped: n = 3 (N - 1) unknowns, node v's at 3 (v - 1).
+ *      damp_t, damp_t, damp_r are added to each node's three diagonal elements, after the sums.  LDL^T,
+ *      right-looking on the lower triangle: for column p = 0..n-1, d_p = H[p][p] must be > 0 and
+ *      finite; l_ap = H[a][p] / d_p for a > p; H[a][b] = H[a][b] - l_ap H[b][p] for p < b <= a, with
+ *      H[b][p] the undivided value: one product and one subtraction per p.  Forward: y_a = g_a minus
+ *      l_ab y_b, one b at a time in ascending b < a.  z_a = y_a / d_a.  Back: x_a = z_a minus l_ba x_b,
+ *      one b at a time in descending b > a.  delta = -x; the stepped pose of a node v >= 1 is
+ *      x_v + delta_v, component by component, with no angle wrap; node 0 keeps its bits.  On a pivot
+ *      that fails (the first one ends the solve) or a stepped component that is not finite:
+ *      LSLAM_POSEGRAPH_SINGULAR, the poses stay, and the iteration ends here.  Otherwise the poses
+ *      become the stepped poses, iters = k + 1, and LSLAM_POSEGRAPH_CONVERGED is set iff
+ *      |delta| < eps_t for every x and y component and |delta| < eps_r for every theta component.
+ *   3. Gate.  LSLAM_POSEGRAPH_DIVERGED iff not (chi2_last <= chi2_0), the last and the first
+ *      evaluation made (a NaN fails).
+ *   4. Outputs.  pose_out = the poses as they stand for nodes < N, unless LSLAM_POSEGRAPH_SINGULAR or
+ *      LSLAM_POSEGRAPH_DIVERGED is set: then pose bit for bit.  The slabs of nodes >= N are copied
+ *      through.  chi2 = (chi2_0, chi2_last); trace rows beyond the last evaluation, and the entries of
+ *      nodes >= N and of edges >= E, are zeros.
+ * z is the pose of j seen from i: z = (R(theta_i)^T (p_j - p_i), theta_j - theta_i), and Omega is the
+ * information of that measurement in i's frame.  The solve is dense: 3 (N_cap - 1) <= 189 unknowns in
+ * the workgroup's LDS (lslam_posegraph.h), which is what bounds max_nodes.  There is no robust kernel:
+ * a false closure pulls the whole graph, and shows as the largest edge_chi2.  One launch behind the
+ * memsets of trace, chi2, edge_chi2 and iters, one workgroup per graph; only that workgroup reads the
+ * graph's pose, and it writes pose_out last, so pose_out may be pose.  Runs on the context's main
+ * stream, after every earlier call, with no host synchronisation inside; there is no timing slot.
+ * Out-of-range parameters and missing pointers return LSLAM_ERR_ARG (the message names the field),
+ * checked before the context is touched; n_graphs == 0 does nothing. */
+int lslam_pose_graph(lslam_ctx *ctx, const lslam_posegraph_batch *b, const lslam_posegraph_params *p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,9 @@ lidar_slam_amd.mapping.GridRayCaster (the grid read beam by beam: expected retur
 lidar_slam_amd.mapping.DistanceField (the grid's exact distance field: clearance, a revolution's distance to the map,
 its Gauss-Newton alignment there, and ``fuse``: that alignment as a gated Kalman update of the filter),
 lidar_slam_amd.localize.GridLocalizer (scan-to-map matching: the pose corrected against the robot's grid),
-lidar_slam_amd.localize.GridRelocalizer (global relocalisation: the pose found in the grid without a guess).
+lidar_slam_amd.localize.GridRelocalizer (global relocalisation: the pose found in the grid without a guess),
+lidar_slam_amd.posegraph.PoseGraph (loop closure: a pose graph per robot optimised on the device, with
+``posegraph.relative_pose`` and ``posegraph.closure_edge`` for its edges; ``OccupancyGrid.redraw`` draws the map again
+from the corrected keyframes).
 """
 __version__ = "0.1.0"

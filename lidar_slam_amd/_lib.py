@@ -51,6 +51,7 @@ MERGE_ADD, MERGE_FILL = 0, 1  # lslam_gridmerge_params.mode
 MERGE_MERGED, MERGE_WEAK, MERGE_CONFLICT, MERGE_SKIPPED, MERGE_BAD_XFORM = 1, 2, 4, 8, 16
 GRIDPOINTS_BAD_ANCHOR, GRIDPOINTS_EMPTY, GRIDPOINTS_DECIMATED = 1, 2, 4
 GRIDPOINTS_BANDS = 256  # LSLAM_GRIDPOINTS_BANDS: the second dimension of lslam_gridpoints_batch.band_counts
+POSEGRAPH_EMPTY, POSEGRAPH_BAD_GRAPH, POSEGRAPH_CONVERGED, POSEGRAPH_SINGULAR, POSEGRAPH_DIVERGED = 1, 2, 4, 8, 16
 
 
 class HIPLibraryError(RuntimeError):
@@ -245,6 +246,17 @@ class GridPointsBatch(C.Structure):
                [(n, _VP) for n in ("logodds", "origin", "anchor", "xy", "pt_off", "counts", "flags", "band_counts")]
 
 
+class PoseGraphParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("damp_t", "damp_r", "eps_t", "eps_r")] + \
+               [(n, C.c_int32) for n in ("max_nodes", "max_edges", "n_iter", "reserved")]
+
+
+class PoseGraphBatch(C.Structure):
+    _fields_ = [("n_graphs", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, _VP) for n in ("n_nodes", "n_edges", "pose", "edge_ij", "edge_z", "edge_info", "pose_out", "trace", "chi2",
+                                   "edge_chi2", "iters", "flags")]
+
+
 assert C.sizeof(ChunkModel) == 112
 assert C.sizeof(LandmarkRec) == 56
 
@@ -273,6 +285,7 @@ EXPORTS = [
     "lslam_grid_page_load",
     "lslam_gridmerge_abi_sizes", "lslam_gridmerge_params_default", "lslam_grid_merge",
     "lslam_gridpoints_abi_sizes", "lslam_gridpoints_params_default", "lslam_grid_points",
+    "lslam_posegraph_abi_sizes", "lslam_posegraph_params_default", "lslam_pose_graph",
 ]
 
 _lib = None
@@ -384,6 +397,9 @@ def load():
         "lslam_gridpoints_abi_sizes": ([P(i64), C.c_int], C.c_int),
         "lslam_gridpoints_params_default": ([P(GridPointsParams)], C.c_int),
         "lslam_grid_points": ([_VP, P(GridPointsBatch), P(GridParams), P(GridPointsParams)], C.c_int),
+        "lslam_posegraph_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_posegraph_params_default": ([P(PoseGraphParams)], C.c_int),
+        "lslam_pose_graph": ([_VP, P(PoseGraphBatch), P(PoseGraphParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -438,6 +454,7 @@ _ABI_SIZES = [
     ("lslam_page_abi_sizes", (PageParams, PageBatch)),
     ("lslam_gridmerge_abi_sizes", (GridMergeParams, GridMergeBatch)),
     ("lslam_gridpoints_abi_sizes", (GridPointsParams, GridPointsBatch)),
+    ("lslam_posegraph_abi_sizes", (PoseGraphParams, PoseGraphBatch)),
 ]
 
 
@@ -503,6 +520,7 @@ relocprior_params = _params_factory("relocprior", RelocPriorParams)
 page_params = _params_factory("page", PageParams)
 gridmerge_params = _params_factory("gridmerge", GridMergeParams)
 gridpoints_params = _params_factory("gridpoints", GridPointsParams)
+posegraph_params = _params_factory("posegraph", PoseGraphParams)
 
 
 def ukf_params(n_landmarks, **kw):

@@ -21,7 +21,9 @@
 //   lslam_gridmerge.h (the map merge: one grid gathered into another's frame, gated and added; its
 //   tiles, gather arithmetic, classes and merged value are lslam_gridmerge_plan.h, plain C++),
 //   lslam_gridpoints.h (a map read as a revolution: a grid's occupied cells about an anchor pose,
-//   compacted in order; its bands, range test, point and stride are lslam_gridpoints_plan.h, plain C++);
+//   compacted in order; its bands, range test, point and stride are lslam_gridpoints_plan.h, plain C++),
+//   lslam_posegraph.h (loop closure: a pose graph per robot solved by Gauss-Newton in LDS; its edge terms,
+//   packed triangle and LDL^T steps are lslam_posegraph_core.h, plain C++);
 // the host side is included at the foot:
 //   lslam_hazards.h  which waits a call's producer needs (plain C++, no HIP)
 //   lslam_ctx.h      lslam_ctx, its grow-only device buffers and timers, create / destroy,
@@ -3087,7 +3089,10 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
 #include "lslam_relocprior.h"
 // the paged rolling grid's kernels, templates built on the recentre kernel's device functions: the newest
 #include "lslam_page.h"
-// the map-as-revolution kernel, a template: the newest header, included ahead of the merge's; its place in the
+// the pose-graph kernel, a template: the newest header, included ahead of the map-as-revolution one; its place in
+// the code object is launch_posegraph's (lslam_launch_map.h), directly ahead of the four gridpoints kernels
+#include "lslam_posegraph.h"
+// the map-as-revolution kernel, a template, included ahead of the merge's; its place in the
 // code object is launch_gridpoints' (lslam_launch_map.h), directly ahead of the merge's four kernels
 #include "lslam_gridpoints.h"
 // the map merge's kernel, a template; its place in the code object is launch_gridmerge's

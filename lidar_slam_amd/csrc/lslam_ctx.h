@@ -452,6 +452,12 @@ int lslam_gridpoints_abi_sizes(int64_t *sizes, int n) {
     return 2;
 }
 
+int lslam_posegraph_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[2] = {(int64_t)sizeof(lslam_posegraph_params), (int64_t)sizeof(lslam_posegraph_batch)};
+    for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
+    return 2;
+}
+
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
     if (!c || (!dst && n)) return LSLAM_ERR_ARG;
     if (!n) return LSLAM_OK;
@@ -718,6 +724,19 @@ int lslam_gridpoints_params_default(lslam_gridpoints_params *p) {
     p->radius = 8000.0;  // the grid's default max_range: the matchers drop what lies further
     p->occ_min = 85;     // one hit: the matchers' and the merge's threshold
     p->cap = 1024;       // slots: the L-shaped room's 827 cells in range fit (tests/test_gridpoints_ref.py)
+    return LSLAM_OK;
+}
+
+int lslam_posegraph_params_default(lslam_posegraph_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->damp_t = 1e-6;    // 1/mm^2: a prior of one metre on a node that no edge holds
+    p->damp_r = 1e-3;    // 1/rad^2: some thirty radians, likewise
+    p->eps_t = 0.01;     // mm: far below a keyframe's own uncertainty
+    p->eps_r = 1e-5;     // rad: 0.01 mm at a lever arm of one metre
+    p->max_nodes = 48;   // keyframes a graph: 20 KiB ... 81 KiB of LDS, one to several workgroups a CU
+    p->max_edges = 256;
+    p->n_iter = 10;
     return LSLAM_OK;
 }
 

@@ -950,6 +950,54 @@ static int launch_fieldfuse(lslam_ctx *c, const lslam_fieldfuse_batch *b, const 
                          {b->nis, n * 8}});
 }
 
+// ---- pose-graph optimisation (lslam_posegraph.h) ----
+// Between launch_fieldfuse and launch_gridpoints: a kernel template is emitted where it is first used, and
+// tests/test_gridpoints_budget.py holds the four gridpoints kernels to the places -11..-8 of the code object.  Here
+// the one instantiation stands directly ahead of those four; the kernels behind it keep their bytes.
+
+static int posegraph_check_params(const lslam_posegraph_params *p) {
+    if (!p) return set_err(LSLAM_ERR_ARG, "posegraph: params is NULL");
+    if (p->max_nodes < 2 || p->max_nodes > POSEGRAPH_MAX_NODES) return set_err(LSLAM_ERR_ARG, "posegraph: max_nodes must be in [2, 64]");
+    if (p->max_edges < 1 || p->max_edges > POSEGRAPH_MAX_EDGES) return set_err(LSLAM_ERR_ARG, "posegraph: max_edges must be in [1, 1024]");
+    if (p->n_iter < 0 || p->n_iter > POSEGRAPH_MAX_ITER) return set_err(LSLAM_ERR_ARG, "posegraph: n_iter must be in [0, 32]");
+    if (!(p->damp_t >= 0.0) || !std::isfinite(p->damp_t)) return set_err(LSLAM_ERR_ARG, "posegraph: damp_t must be >= 0 and finite");
+    if (!(p->damp_r >= 0.0) || !std::isfinite(p->damp_r)) return set_err(LSLAM_ERR_ARG, "posegraph: damp_r must be >= 0 and finite");
+    if (!(p->eps_t >= 0.0) || !std::isfinite(p->eps_t)) return set_err(LSLAM_ERR_ARG, "posegraph: eps_t must be >= 0 and finite");
+    if (!(p->eps_r >= 0.0) || !std::isfinite(p->eps_r)) return set_err(LSLAM_ERR_ARG, "posegraph: eps_r must be >= 0 and finite");
+    return LSLAM_OK;
+}
+
+static Reqs posegraph_reqs(const lslam_posegraph_batch &b) {
+    return {{{"n_nodes", b.n_nodes}, {"n_edges", b.n_edges}, {"pose", b.pose}, {"edge_ij", b.edge_ij}, {"edge_z", b.edge_z},
+             {"edge_info", b.edge_info}},
+            {{"pose_out", b.pose_out}, {"trace", b.trace}, {"chi2", b.chi2}, {"edge_chi2", b.edge_chi2}, {"iters", b.iters},
+             {"flags", b.flags}},
+            b.n_graphs,
+            "n_graphs"};
+}
+
+// One workgroup per graph; the LDS is sized from max_nodes and max_edges.
+static int launch_posegraph(lslam_ctx *c, const lslam_posegraph_batch *b, const lslam_posegraph_params *p) {
+    PoseGraphArgs k;
+    memset(&k, 0, sizeof(k));
+    k.b = *b;
+    k.p = *p;
+    const int lds = posegraph_lds_bytes(p->max_nodes, p->max_edges);
+    if (lds > POSEGRAPH_LDS_MAX) return set_err(LSLAM_ERR_UNSUPPORTED, "posegraph: max_nodes and max_edges do not fit LDS");
+    const size_t n = (size_t)b->n_graphs, Nc = (size_t)p->max_nodes, Ec = (size_t)p->max_edges, rows = (size_t)p->n_iter + 1;
+    int st = check_blocks("posegraph", (int64_t)b->n_graphs);
+    if (st) return st;
+    // (pose_out and flags are written for every graph; the rest is zeros where the kernel writes nothing)
+    if ((st = note_outs(c, {{b->pose_out, Nc * n * 24}, {b->trace, n * rows * Nc * 16, true}, {b->chi2, n * 16, true},
+                            {b->edge_chi2, n * Ec * 8, true}, {b->iters, n * 4, true}, {b->flags, n * 4}})))
+        return st;
+    static std::once_flag once;
+    std::call_once(once, [] { set_max_lds(posegraph_kernel<0>); });
+    hipLaunchKernelGGL(posegraph_kernel<0>, dim3((unsigned)n), dim3(POSEGRAPH_TPB), lds, c->stream, k);
+    HIPCHK(hipGetLastError());
+    return LSLAM_OK;
+}
+
 // ---- a map as a revolution (lslam_gridpoints.h) ----
 // Between launch_fieldfuse and launch_gridmerge: a kernel template is emitted where it is first used, and
 // tests/test_gridmerge_budget.py holds the merge's four kernels to the places -7..-4 of the code object.  Here the
@@ -1377,6 +1425,14 @@ int lslam_grid_points(lslam_ctx *c, const lslam_gridpoints_batch *b, const lslam
             return LSLAM_OK;
         },
         [&] { return launch_gridpoints(c, b, g, p); });
+}
+
+// On the main stream: after the calls that wrote the poses and the edges, before the calls that read pose_out
+// (a slab of it is a pose of lslam_grid_update and of the matchers).
+int lslam_pose_graph(lslam_ctx *c, const lslam_posegraph_batch *b, const lslam_posegraph_params *p) {
+    int st = posegraph_check_params(p);
+    if (st) return st;
+    return map_entry("posegraph", c, b, posegraph_reqs, [&] { return launch_posegraph(c, b, p); });
 }
 
 // (the scratch is sized per call: a call in flight keeps the chunking it was launched with)

@@ -334,6 +334,24 @@ class OccupancyGrid:
         """Zero every grid (unknown everywhere), on the stream."""
         self.logodds.fill_zero()
 
+    def redraw(self, graph, sync=True):
+        """Draw every grid again from a ``PoseGraph``'s keyframes: ``clear``, then one ``step`` per
+        keyframe from the revolution stored with it at ``graph.node_pose(k)``, the corrected poses read on
+        the device in stream order (after a ``graph.solve(sync=False)`` too).  Every keyframe is replayed,
+        and only keyframes: what was drawn between them is gone.  A keyframe stored without a revolution
+        is an error.  (Host revolutions are staged as ``step`` stages them.)"""
+        if graph.G != self.R:
+            raise ValueError("the graph holds %d robots, the grid %d" % (graph.G, self.R))
+        revs = graph.revolutions[:graph.n]
+        if any(r is None for r in revs):
+            raise ValueError("a keyframe was stored without its revolution")
+        self.clear()
+        for k, rev in enumerate(revs):
+            args = rev if isinstance(rev, (tuple, list)) else (rev,)
+            self.step(*args, pose=graph.node_pose(k), sync=False)
+        if sync:
+            self.ctx.sync()
+
     def upload(self, logodds):
         """Replace the grids (tests, restarts): int16 [R, W, W]."""
         self.logodds.upload(np.ascontiguousarray(logodds, np.int16).reshape(self.R, self.W, self.W))
