@@ -1606,14 +1606,114 @@ int lslam_posegraph_params_default(lslam_posegraph_params *p);
  *      nodes >= N and of edges >= E, are zeros.
  * z is the pose of j seen from i: z = (R(theta_i)^T (p_j - p_i), theta_j - theta_i), and Omega is the
  * information of that measurement in i's frame.  The solve is dense: 3 (N_cap - 1) <= 189 unknowns in
- * the workgroup's LDS (lslam_posegraph.h), which is what bounds max_nodes.  There is no robust kernel:
- * a false closure pulls the whole graph, and shows as the largest edge_chi2.  One launch behind the
+ * the workgroup's LDS (lslam_posegraph.h), which is what bounds max_nodes.  The solve has no robust kernel:
+ * a false closure that reaches it pulls the whole graph (and shows as the largest edge_chi2 only when it
+ * is weighted no more strongly than the odometry), so it is rejected before, by lslam_pose_graph_gate.  One launch behind the
  * memsets of trace, chi2, edge_chi2 and iters, one workgroup per graph; only that workgroup reads the
  * graph's pose, and it writes pose_out last, so pose_out may be pose.  Runs on the context's main
  * stream, after every earlier call, with no host synchronisation inside; there is no timing slot.
  * Out-of-range parameters and missing pointers return LSLAM_ERR_ARG (the message names the field),
  * checked before the context is touched; n_graphs == 0 does nothing. */
 int lslam_pose_graph(lslam_ctx *ctx, const lslam_posegraph_batch *b, const lslam_posegraph_params *p);
+
+/* ---- closure gating (lslam_pose_graph_gate): a candidate's verdict (lslam_posegate_batch.cand_flags) ---- */
+enum {
+    LSLAM_POSEGATE_UNJUDGED = 0,  /* no verdict: the slot is beyond n_cand, or the graph is flagged */
+    LSLAM_POSEGATE_ACCEPTED = 1,  /* d2 <= nis_max */
+    LSLAM_POSEGATE_OUTLIER = 2,   /* not (d2 <= nis_max); a NaN among them */
+    LSLAM_POSEGATE_BAD_EDGE = 4,  /* i = j, an index outside 0..N-1, or a z or an Omega that is not finite: nis, err and cov are zero */
+    LSLAM_POSEGATE_BAD_INFO = 8,  /* Omega or the innovation covariance has no positive inverse: nis is zero */
+    LSLAM_POSEGATE_APPENDED = 16, /* beside ACCEPTED, with append: the candidate is now an edge of the graph */
+    LSLAM_POSEGATE_NO_ROOM = 32   /* beside ACCEPTED, with append: the graph already held max_edges edges */
+};
+
+/* Closure gating (lslam_pose_graph_gate), 40 bytes. */
+typedef struct lslam_posegate_params {
+    double damp_t;     /* as lslam_posegraph_params: what the solve that follows will use (1e-6) */
+    double damp_r;     /* (1e-3) */
+    double nis_max;    /* the gate on d2; > 0, +inf: every candidate with a statistic is accepted (16.27: chi-square, 3 dof, 0.1 %) */
+    int32_t max_nodes; /* N_cap: the node dimension of pose and trace; 2..64 (48) */
+    int32_t max_edges; /* E_cap: the edge dimension of edge_ij, edge_z and edge_info; 1..1024 (256) */
+    int32_t max_cand;  /* C_cap: the candidate dimension of every cand_ array; 1..64 (16) */
+    int32_t append;    /* 0: the edge arrays and n_edges are only read; 1: the accepted candidates become edges (0) */
+} lslam_posegate_params;
+
+/* One graph per robot and its closure candidates, 144 bytes; all pointers DEVICE memory; all required.  The
+ * graph is what lslam_posegraph_batch holds, in that layout, so that the same buffers serve both calls. */
+typedef struct lslam_posegate_batch {
+    int32_t n_graphs;
+    int32_t reserved;
+    const int32_t *n_nodes;  /* [G] */
+    int32_t *n_edges;        /* [G]; with append also an output */
+    const double *pose;      /* [N_cap][G][3] node-major: the poses at which the graph is linearised */
+    int32_t *edge_ij;        /* [G][E_cap][2]; with append also an output, as edge_z and edge_info */
+    double *edge_z;          /* [G][E_cap][3] */
+    double *edge_info;       /* [G][E_cap][6] */
+    const int32_t *n_cand;   /* [G] */
+    const int32_t *cand_ij;  /* [G][C_cap][2] */
+    const double *cand_z;    /* [G][C_cap][3] */
+    const double *cand_info; /* [G][C_cap][6] xx, xy, xt, yy, yt, tt */
+    double *trace;           /* [G][N_cap][2] (cos, sin) of every node at the evaluation, zeros beyond */
+    double *chi2;            /* [G] of the graph at pose, without the candidates */
+    double *cand_nis;        /* [G][C_cap] d2 */
+    double *cand_err;        /* [G][C_cap][3] e */
+    double *cand_cov;        /* [G][C_cap][6] sym(J Sigma J^T) as xx, xy, xt, yy, yt, tt */
+    int32_t *cand_flags;     /* [G][C_cap] LSLAM_POSEGATE_* */
+    int32_t *flags;          /* [G] 0, LSLAM_POSEGRAPH_EMPTY, LSLAM_POSEGRAPH_BAD_GRAPH or LSLAM_POSEGRAPH_SINGULAR */
+} lslam_posegate_batch;
+
+/* lslam_abi_sizes for lslam_posegate_params, lslam_posegate_batch.  Writes min(n, 2) entries, returns 2. */
+int lslam_posegate_abi_sizes(int64_t *sizes, int n);
+int lslam_posegate_params_default(lslam_posegate_params *p);
+
+/* Closure gating: every candidate edge of a graph is judged, before any solve, against what the graph
+ * without it predicts.  With Sigma the covariance of the trusted graph linearised at pose (the inverse of
+ * the damped H of lslam_pose_graph) and J the candidate's Jacobian, the statistic is the innovation
+ * d2 = e^T (J Sigma J^T + Omega_c^-1)^-1 e, chi-square with three degrees of freedom for a true closure on a
+ * calibrated graph: the test lslam_field_fuse applies to a filter measurement.  J Sigma J^T alone, cand_cov,
+ * does not depend on z: it is the covariance of where node j is expected in node i's frame, the window in
+ * which to look for the closure.  N_cap = max_nodes, E_cap = max_edges, C_cap = max_cand.  All FP64, every
+ * operation rounded on its own (nothing is fused), every sum in the order written.  Per graph, N = n_nodes,
+ * E = n_edges, C = n_cand:
+ *   0. Checks.  LSLAM_POSEGRAPH_BAD_GRAPH if N < 0, E < 0, N > N_cap, E > E_cap, C < 0 or C > C_cap; else
+ *      LSLAM_POSEGRAPH_EMPTY if N < 2 or E = 0; else LSLAM_POSEGRAPH_BAD_GRAPH by lslam_pose_graph's test
+ *      of the edges 0..E-1 and of the poses 0..N-1.  With either flag every candidate stays
+ *      LSLAM_POSEGATE_UNJUDGED, every output of the graph but flags is zero and nothing is appended.
+ *   1. One evaluation at pose, bit for bit lslam_pose_graph's step 1: (c_i, s_i) = the library's cos and
+ *      sin of theta_i, written to trace[g][i] for i < N (the written bits are the definition's input); H and
+ *      g from the edges in ascending e, then damp_t, damp_t, damp_r on every free node's diagonal.
+ *      chi2[g] = the sum of chi_e from +0.0 in ascending e: where it is the graph's minimum, pose is the
+ *      optimum and Sigma means what it should.
+ *   2. The LDL^T of lslam_pose_graph's step 2 on the reduced H (node 0 is the gauge, n = 3 (N - 1)), with
+ *      the same element steps.  A pivot that is not finite and > 0 (the first one ends the call for this
+ *      graph): LSLAM_POSEGRAPH_SINGULAR; trace and chi2 stay as step 1 wrote them, every candidate stays
+ *      LSLAM_POSEGATE_UNJUDGED with zero outputs and nothing is appended.
+ *   3. Each candidate c < C = (i, j, z, Omega).  LSLAM_POSEGATE_BAD_EDGE, with zero nis, err and cov, if
+ *      i = j, an index is outside 0..N-1, or a component of z or Omega is not finite.  Otherwise e, A and B
+ *      of lslam_pose_graph's step 1 at (x_i, x_j, c_i, s_i, z).  R = J^T, n x 3: rows 3 (i - 1).. hold A^T
+ *      if i >= 1, rows 3 (j - 1).. hold B^T if j >= 1, every other row is +0.0.  X = H^-1 R, each column
+ *      as step 2 of lslam_pose_graph solves for g: forward, divide, back.  M = J X: element (r, k) sums,
+ *      from +0.0, A[r][q] X[3 (i - 1) + q][k] over q = 0, 1, 2 if i >= 1, then B[r][q] X[3 (j - 1) + q][k]
+ *      likewise if j >= 1 (the gauge contributes nothing).  Ms = 0.5 (M + M^T).  Sc = Omega^-1 and then
+ *      Si = (Ms + Sc)^-1, both by the adjugate and the determinant of lslam_map_fuse's step 7 and its pass
+ *      test; w = Si e, each element (t0 + t1) + t2; d2 = (e0 w0 + e1 w1) + e2 w2.  cand_err = e and
+ *      cand_cov = Ms.  If either inverse fails its test: LSLAM_POSEGATE_BAD_INFO alone and cand_nis = 0.
+ *      Otherwise cand_nis = d2, and LSLAM_POSEGATE_ACCEPTED iff d2 <= nis_max (a NaN fails), else
+ *      LSLAM_POSEGATE_OUTLIER.  The entries of c >= C are zeros.
+ *   4. With append: in ascending c, an ACCEPTED candidate is copied to the edge arrays at index E, E grows
+ *      by one and the candidate gains LSLAM_POSEGATE_APPENDED, while E < E_cap; after that it gains
+ *      LSLAM_POSEGATE_NO_ROOM.  n_edges[g] = E.  Without append the edge arrays and n_edges are only read.
+ * Known limits.  Candidates are judged one by one against the trusted graph, not against each other: two
+ * candidates that agree with the graph and contradict one another both pass.  Sigma is the linearised
+ * covariance at pose, with the damping in it as a weak prior on every node.  A graph whose odometry
+ * information is overconfident rejects true closures.  The solve is still dense, 3 (N_cap - 1) <= 189
+ * unknowns in the workgroup's LDS (lslam_posegate.h); a max_nodes, max_edges and max_cand whose LDS does
+ * not fit return LSLAM_ERR_UNSUPPORTED.  One launch behind the memsets of every output but flags, one
+ * workgroup per graph.  Runs on the context's main stream, after every earlier call, with no host
+ * synchronisation inside; there is no timing slot.  Out-of-range parameters and missing pointers return
+ * LSLAM_ERR_ARG (the message names the field), checked before the context is touched; n_graphs == 0 does
+ * nothing. */
+int lslam_pose_graph_gate(lslam_ctx *ctx, const lslam_posegate_batch *b, const lslam_posegate_params *p);
 
 #ifdef __cplusplus
 }

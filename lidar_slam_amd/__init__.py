@@ -26,6 +26,8 @@ lidar_slam_amd.localize.GridLocalizer (scan-to-map matching: the pose corrected 
 lidar_slam_amd.localize.GridRelocalizer (global relocalisation: the pose found in the grid without a guess),
 lidar_slam_amd.posegraph.PoseGraph (loop closure: a pose graph per robot optimised on the device, with
 ``posegraph.relative_pose`` and ``posegraph.closure_edge`` for its edges; ``OccupancyGrid.redraw`` draws the map again
-from the corrected keyframes).
+from the corrected keyframes; ``PoseGraph.propose`` and ``PoseGraph.gate`` judge closure candidates by their innovation
+against the graph before they become edges, ``PoseGraph.relative_covariance`` with ``posegraph.closure_window`` gives the
+window in which to look for a closure).
 """
 __version__ = "0.1.0"

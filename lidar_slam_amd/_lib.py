@@ -52,6 +52,8 @@ MERGE_MERGED, MERGE_WEAK, MERGE_CONFLICT, MERGE_SKIPPED, MERGE_BAD_XFORM = 1, 2,
 GRIDPOINTS_BAD_ANCHOR, GRIDPOINTS_EMPTY, GRIDPOINTS_DECIMATED = 1, 2, 4
 GRIDPOINTS_BANDS = 256  # LSLAM_GRIDPOINTS_BANDS: the second dimension of lslam_gridpoints_batch.band_counts
 POSEGRAPH_EMPTY, POSEGRAPH_BAD_GRAPH, POSEGRAPH_CONVERGED, POSEGRAPH_SINGULAR, POSEGRAPH_DIVERGED = 1, 2, 4, 8, 16
+POSEGATE_UNJUDGED, POSEGATE_ACCEPTED, POSEGATE_OUTLIER, POSEGATE_BAD_EDGE, POSEGATE_BAD_INFO = 0, 1, 2, 4, 8
+POSEGATE_APPENDED, POSEGATE_NO_ROOM = 16, 32  # beside POSEGATE_ACCEPTED
 
 
 class HIPLibraryError(RuntimeError):
@@ -257,6 +259,17 @@ class PoseGraphBatch(C.Structure):
                                    "edge_chi2", "iters", "flags")]
 
 
+class PoseGateParams(C.Structure):
+    _fields_ = [(n, C.c_double) for n in ("damp_t", "damp_r", "nis_max")] + \
+               [(n, C.c_int32) for n in ("max_nodes", "max_edges", "max_cand", "append")]
+
+
+class PoseGateBatch(C.Structure):
+    _fields_ = [("n_graphs", C.c_int32), ("reserved", C.c_int32)] + \
+               [(n, _VP) for n in ("n_nodes", "n_edges", "pose", "edge_ij", "edge_z", "edge_info", "n_cand", "cand_ij", "cand_z",
+                                   "cand_info", "trace", "chi2", "cand_nis", "cand_err", "cand_cov", "cand_flags", "flags")]
+
+
 assert C.sizeof(ChunkModel) == 112
 assert C.sizeof(LandmarkRec) == 56
 
@@ -286,6 +299,7 @@ EXPORTS = [
     "lslam_gridmerge_abi_sizes", "lslam_gridmerge_params_default", "lslam_grid_merge",
     "lslam_gridpoints_abi_sizes", "lslam_gridpoints_params_default", "lslam_grid_points",
     "lslam_posegraph_abi_sizes", "lslam_posegraph_params_default", "lslam_pose_graph",
+    "lslam_posegate_abi_sizes", "lslam_posegate_params_default", "lslam_pose_graph_gate",
 ]
 
 _lib = None
@@ -400,6 +414,9 @@ def load():
         "lslam_posegraph_abi_sizes": ([P(i64), C.c_int], C.c_int),
         "lslam_posegraph_params_default": ([P(PoseGraphParams)], C.c_int),
         "lslam_pose_graph": ([_VP, P(PoseGraphBatch), P(PoseGraphParams)], C.c_int),
+        "lslam_posegate_abi_sizes": ([P(i64), C.c_int], C.c_int),
+        "lslam_posegate_params_default": ([P(PoseGateParams)], C.c_int),
+        "lslam_pose_graph_gate": ([_VP, P(PoseGateBatch), P(PoseGateParams)], C.c_int),
     }
     try:
         for name, (args, res) in sig.items():
@@ -455,6 +472,7 @@ _ABI_SIZES = [
     ("lslam_gridmerge_abi_sizes", (GridMergeParams, GridMergeBatch)),
     ("lslam_gridpoints_abi_sizes", (GridPointsParams, GridPointsBatch)),
     ("lslam_posegraph_abi_sizes", (PoseGraphParams, PoseGraphBatch)),
+    ("lslam_posegate_abi_sizes", (PoseGateParams, PoseGateBatch)),
 ]
 
 
@@ -521,6 +539,7 @@ page_params = _params_factory("page", PageParams)
 gridmerge_params = _params_factory("gridmerge", GridMergeParams)
 gridpoints_params = _params_factory("gridpoints", GridPointsParams)
 posegraph_params = _params_factory("posegraph", PoseGraphParams)
+posegate_params = _params_factory("posegate", PoseGateParams)
 
 
 def ukf_params(n_landmarks, **kw):

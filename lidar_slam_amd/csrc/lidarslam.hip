@@ -24,6 +24,8 @@
 //   compacted in order; its bands, range test, point and stride are lslam_gridpoints_plan.h, plain C++),
 //   lslam_posegraph.h (loop closure: a pose graph per robot solved by Gauss-Newton in LDS; its edge terms,
 //   packed triangle and LDL^T steps are lslam_posegraph_core.h, plain C++);
+//   lslam_posegate.h (closure gating: a candidate edge's innovation against the graph without it; its
+//   right-hand sides and 3 x 3 tail are lslam_posegate_core.h, plain C++);
 // the host side is included at the foot:
 //   lslam_hazards.h  which waits a call's producer needs (plain C++, no HIP)
 //   lslam_ctx.h      lslam_ctx, its grow-only device buffers and timers, create / destroy,
@@ -3092,6 +3094,9 @@ __global__ __launch_bounds__(256) void polar_kernel(const double *__restrict__ t
 // the pose-graph kernel, a template: the newest header, included ahead of the map-as-revolution one; its place in
 // the code object is launch_posegraph's (lslam_launch_map.h), directly ahead of the four gridpoints kernels
 #include "lslam_posegraph.h"
+// the closure gate's kernel, a template on the pose-graph kernel's device functions; its place in the code object
+// is launch_posegate's (lslam_launch_map.h), directly ahead of the pose-graph kernel
+#include "lslam_posegate.h"
 // the map-as-revolution kernel, a template, included ahead of the merge's; its place in the
 // code object is launch_gridpoints' (lslam_launch_map.h), directly ahead of the merge's four kernels
 #include "lslam_gridpoints.h"

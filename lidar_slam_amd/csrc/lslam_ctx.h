@@ -458,6 +458,12 @@ int lslam_posegraph_abi_sizes(int64_t *sizes, int n) {
     return 2;
 }
 
+int lslam_posegate_abi_sizes(int64_t *sizes, int n) {
+    const int64_t s[2] = {(int64_t)sizeof(lslam_posegate_params), (int64_t)sizeof(lslam_posegate_batch)};
+    for (int i = 0; i < n && i < 2 && sizes; i++) sizes[i] = s[i];
+    return 2;
+}
+
 int lslam_memset(lslam_ctx *c, void *dst, int v, size_t n) {
     if (!c || (!dst && n)) return LSLAM_ERR_ARG;
     if (!n) return LSLAM_OK;
@@ -737,6 +743,19 @@ int lslam_posegraph_params_default(lslam_posegraph_params *p) {
     p->max_nodes = 48;   // keyframes a graph: 20 KiB ... 81 KiB of LDS, one to several workgroups a CU
     p->max_edges = 256;
     p->n_iter = 10;
+    return LSLAM_OK;
+}
+
+int lslam_posegate_params_default(lslam_posegate_params *p) {
+    if (!p) return LSLAM_ERR_ARG;
+    memset(p, 0, sizeof(*p));
+    p->damp_t = 1e-6;    // lslam_posegraph_params' defaults: the solve that follows uses the same H
+    p->damp_r = 1e-3;
+    p->nis_max = 16.27;  // chi-square, 3 dof, 0.1 %: lslam_fieldfuse_params' gate
+    p->max_nodes = 48;
+    p->max_edges = 256;
+    p->max_cand = 16;    // closures proposed between two solves
+    p->append = 0;
     return LSLAM_OK;
 }
 

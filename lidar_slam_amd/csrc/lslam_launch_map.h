@@ -12,14 +12,14 @@ static int map_err(int code, const char *who, const char *what) {
 }
 
 // A batch's required pointers, inputs then outputs, each list ending at its first empty slot (so at
-// most 7 and 15 names), with the batch's size.  Optional pointers stay out.  The entry frame tests the
+// most 11 and 15 names), with the batch's size.  Optional pointers stay out.  The entry frame tests the
 // pointers and names them in its message from this one list.
 struct Req {
     const char *name;
     const void *p;
 };
 struct Reqs {
-    Req in[8], out[16];
+    Req in[12], out[16];
     int n = 0;
     const char *n_name = "n_robots";
 };
@@ -950,6 +950,61 @@ static int launch_fieldfuse(lslam_ctx *c, const lslam_fieldfuse_batch *b, const 
                          {b->nis, n * 8}});
 }
 
+// ---- closure gating (lslam_posegate.h) ----
+// Between launch_fieldfuse and launch_posegraph: a kernel template is emitted where it is first used, and
+// tests/test_posegraph_budget.py holds the pose-graph kernel to the place -12 of the code object.  Here the one
+// instantiation stands directly ahead of it; the kernels behind it keep their bytes.
+
+static int posegate_check_params(const lslam_posegate_params *p) {
+    if (!p) return set_err(LSLAM_ERR_ARG, "posegate: params is NULL");
+    if (p->max_nodes < 2 || p->max_nodes > POSEGRAPH_MAX_NODES) return set_err(LSLAM_ERR_ARG, "posegate: max_nodes must be in [2, 64]");
+    if (p->max_edges < 1 || p->max_edges > POSEGRAPH_MAX_EDGES) return set_err(LSLAM_ERR_ARG, "posegate: max_edges must be in [1, 1024]");
+    if (p->max_cand < 1 || p->max_cand > POSEGATE_MAX_CAND) return set_err(LSLAM_ERR_ARG, "posegate: max_cand must be in [1, 64]");
+    if (!(p->damp_t >= 0.0) || !std::isfinite(p->damp_t)) return set_err(LSLAM_ERR_ARG, "posegate: damp_t must be >= 0 and finite");
+    if (!(p->damp_r >= 0.0) || !std::isfinite(p->damp_r)) return set_err(LSLAM_ERR_ARG, "posegate: damp_r must be >= 0 and finite");
+    if (!(p->nis_max > 0)) return set_err(LSLAM_ERR_ARG, "posegate: nis_max must be > 0 (+inf: no gate)");
+    if (p->append != 0 && p->append != 1) return set_err(LSLAM_ERR_ARG, "posegate: append must be 0 or 1");
+    return LSLAM_OK;
+}
+
+static Reqs posegate_reqs(const lslam_posegate_batch &b) {
+    return {{{"n_nodes", b.n_nodes}, {"n_edges", b.n_edges}, {"pose", b.pose}, {"edge_ij", b.edge_ij}, {"edge_z", b.edge_z},
+             {"edge_info", b.edge_info}, {"n_cand", b.n_cand}, {"cand_ij", b.cand_ij}, {"cand_z", b.cand_z},
+             {"cand_info", b.cand_info}},
+            {{"trace", b.trace}, {"chi2", b.chi2}, {"cand_nis", b.cand_nis}, {"cand_err", b.cand_err}, {"cand_cov", b.cand_cov},
+             {"cand_flags", b.cand_flags}, {"flags", b.flags}},
+            b.n_graphs,
+            "n_graphs"};
+}
+
+// One workgroup per graph; the LDS is sized from max_nodes, max_edges, max_cand and the candidates of a block.
+static int launch_posegate(lslam_ctx *c, const lslam_posegate_batch *b, const lslam_posegate_params *p) {
+    PoseGateArgs k;
+    memset(&k, 0, sizeof(k));
+    k.b = *b;
+    k.p = *p;
+    k.slots = posegate_slots(p->max_nodes, p->max_edges, p->max_cand);
+    const int lds = posegate_lds_bytes(p->max_nodes, p->max_edges, p->max_cand, k.slots);
+    if (lds > POSEGRAPH_LDS_MAX) return set_err(LSLAM_ERR_UNSUPPORTED, "posegate: max_nodes, max_edges and max_cand do not fit LDS");
+    const size_t n = (size_t)b->n_graphs, Nc = (size_t)p->max_nodes, Ec = (size_t)p->max_edges, Cc = (size_t)p->max_cand;
+    int st = check_blocks("posegate", (int64_t)b->n_graphs);
+    if (st) return st;
+    // (flags is written for every graph; the rest is zeros where the kernel writes nothing.  Without append the edge
+    // arrays and n_edges are only read; with it they are outputs too.)
+    if ((st = note_outs(c, {{b->trace, n * Nc * 16, true}, {b->chi2, n * 8, true}, {b->cand_nis, n * Cc * 8, true},
+                            {b->cand_err, n * Cc * 24, true}, {b->cand_cov, n * Cc * 48, true}, {b->cand_flags, n * Cc * 4, true},
+                            {b->flags, n * 4}})))
+        return st;
+    if (p->append && (st = note_outs(c, {{b->n_edges, n * 4}, {b->edge_ij, n * Ec * 8}, {b->edge_z, n * Ec * 24},
+                                         {b->edge_info, n * Ec * 48}})))
+        return st;
+    static std::once_flag once;
+    std::call_once(once, [] { set_max_lds(posegate_kernel<0>); });
+    hipLaunchKernelGGL(posegate_kernel<0>, dim3((unsigned)n), dim3(POSEGATE_TPB), lds, c->stream, k);
+    HIPCHK(hipGetLastError());
+    return LSLAM_OK;
+}
+
 // ---- pose-graph optimisation (lslam_posegraph.h) ----
 // Between launch_fieldfuse and launch_gridpoints: a kernel template is emitted where it is first used, and
 // tests/test_gridpoints_budget.py holds the four gridpoints kernels to the places -11..-8 of the code object.  Here
@@ -1433,6 +1488,14 @@ int lslam_pose_graph(lslam_ctx *c, const lslam_posegraph_batch *b, const lslam_p
     int st = posegraph_check_params(p);
     if (st) return st;
     return map_entry("posegraph", c, b, posegraph_reqs, [&] { return launch_posegraph(c, b, p); });
+}
+
+// On the main stream, as lslam_pose_graph: after the calls that wrote the poses, the edges and the candidates,
+// before the calls that read the verdicts or, with append, the edges (lslam_pose_graph among them).
+int lslam_pose_graph_gate(lslam_ctx *c, const lslam_posegate_batch *b, const lslam_posegate_params *p) {
+    int st = posegate_check_params(p);
+    if (st) return st;
+    return map_entry("posegate", c, b, posegate_reqs, [&] { return launch_posegate(c, b, p); });
 }
 
 // (the scratch is sized per call: a call in flight keeps the chunking it was launched with)
